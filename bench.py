@@ -19,6 +19,13 @@ What is measured (all real, nothing modeled):
 value = goodput %; config carries ckpt_save_blocking_s / ckpt_restore_s /
 tokens_per_s so the save/restore seconds of the metric name are reported on
 the same line. vs_baseline divides by the reference's 95% goodput headline.
+
+A plain run does only the above. --dump-outputs DIR additionally writes the
+last timed step's loss and a seeded sample of the updated parameters as .npy
+(seeds are fixed, so the inputs repeat from run to run; the midpoint restore
+reloads the latest in-window snapshot, reported as config.ckpt_restored_step).
+--full is where measurements that do not feed the headline figure belong;
+there are none yet, so it changes nothing today.
 """
 
 import argparse
@@ -76,7 +83,51 @@ def parse_args():
                    help="recompute blocks in backward (activation ckpt)")
     p.add_argument("--ckpt-scope", default="full", choices=["full", "model"])
     p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss + a fixed sample of the updated "
+                        "parameters) as DIR/<name>.npy, float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements that do not "
+                        "feed the headline figure (none at present: every "
+                        "field of the result line comes out of the one "
+                        "timed window, so --full adds nothing yet)")
     return p.parse_args()
+
+
+# per-tensor cap of the --dump-outputs parameter sample: ~300 tensors x 16384
+# fp32 values stays near 20 MB for the 8B flagship (limit: 64 MB per dump)
+_DUMP_PER_TENSOR = 16384
+
+
+def dump_outputs(out_dir, rank, world, loss, model):
+    """What a caller of the timed path holds after its last step: the loss
+    that step returned and the parameters its optimizer update left behind.
+    Tensors larger than _DUMP_PER_TENSOR are sampled at seeded indices (same
+    indices every run, in named_parameters order), so two builds run with the
+    same arguments can be compared value for value. FSDP ranks dump their
+    local shards, one file set per rank."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    gen = torch.Generator().manual_seed(4321)
+    chunks = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            t = p.detach()
+            if hasattr(t, "to_local"):
+                t = t.to_local()
+            flat = t.reshape(-1)
+            if flat.numel() > _DUMP_PER_TENSOR:
+                idx = torch.randint(0, flat.numel(), (_DUMP_PER_TENSOR,),
+                                    generator=gen)
+                flat = flat[idx.to(flat.device)]
+            chunks.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, f"loss{suffix}.npy"),
+            loss.detach().float().cpu().numpy().reshape(1))
+    np.save(os.path.join(out_dir, f"params_sample{suffix}.npy"),
+            torch.cat(chunks).numpy())
 
 
 def setup_dist(args):
@@ -254,6 +305,7 @@ def main():
     useful = 0.0
     save_blockings = []
     restore_s = None
+    restored_step = None
     restore_at = args.steps // 2
     hb(f"timed window begin: K={args.steps}")
     step_est = None  # running mean of pure step seconds
@@ -300,7 +352,9 @@ def main():
             assert sd is not None, "no checkpoint in shm to restore from"
             sync()
             restore_s = time.perf_counter() - t0
-            hb(f"restore @ step {k + 1}: {restore_s:.2f} s")
+            restored_step = sd.get("step")
+            hb(f"restore @ step {k + 1}: {restore_s:.2f} s "
+               f"(snapshot of step {restored_step})")
     if cp is not None:
         cp.engine.shm_handler.wait_drained()
     sync()
@@ -322,6 +376,10 @@ def main():
     goodput = 100.0 * useful / t_total
     tokens = world * args.steps * args.batch * args.seq
     loss_val = float(loss.item())
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, loss, model)
+        hb(f"outputs dumped to {args.dump_outputs}")
 
     if cp is not None:
         cp.close()
@@ -359,6 +417,9 @@ def main():
                     else None
                 ),
                 "ckpt_restore_s": round(restore_s, 4) if restore_s else None,
+                # which snapshot the midpoint restore reloaded: the dumped
+                # outputs of two runs are comparable only when this matches
+                "ckpt_restored_step": restored_step,
                 "tokens_per_s": round(tokens / t_total, 1),
                 "final_loss": round(loss_val, 4),
             },

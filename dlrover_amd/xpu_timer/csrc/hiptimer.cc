@@ -706,6 +706,35 @@ hipError_t hipExtModuleLaunchKernel(hipFunction_t f, unsigned gx, unsigned gy,
 // hipblasLtMatmul(handle, desc, alpha, A, Adesc, B, Bdesc, beta, C, Cdesc,
 //                 D, Ddesc, algo, workspace, wsSize, stream)
 // layout attribute query (hipblaslt.h): BATCH_COUNT=0, ROWS=4, COLS=5
+//
+// Current hipBLASLt answers the ROWS/COLS queries with INVALID_VALUE (only
+// the batch attributes are readable), so rows/cols are remembered when the
+// layout is created and the query is only the fallback.
+static std::mutex g_layout_mu;
+static std::map<void*, std::pair<uint64_t, uint64_t>> g_layout_dims;
+
+int hipblasLtMatrixLayoutCreate(void** layout, int type, uint64_t rows,
+                                uint64_t cols, int64_t ld) {
+  using fn_t = int (*)(void**, int, uint64_t, uint64_t, int64_t);
+  static fn_t fn = (fn_t)real("hipblasLtMatrixLayoutCreate");
+  int rc = fn(layout, type, rows, cols, ld);
+  if (rc == 0 && layout != nullptr && *layout != nullptr) {
+    std::lock_guard<std::mutex> g(g_layout_mu);
+    g_layout_dims[*layout] = {rows, cols};
+  }
+  return rc;
+}
+
+int hipblasLtMatrixLayoutDestroy(void* layout) {
+  using fn_t = int (*)(void*);
+  static fn_t fn = (fn_t)real("hipblasLtMatrixLayoutDestroy");
+  {
+    std::lock_guard<std::mutex> g(g_layout_mu);
+    g_layout_dims.erase(layout);
+  }
+  return fn(layout);
+}
+
 static void layout_dims(void* layout, long long* rows, long long* cols,
                         int* batch) {
   using get_t = int (*)(void*, int, void*, size_t, size_t*);
@@ -716,8 +745,20 @@ static void layout_dims(void* layout, long long* rows, long long* cols,
   unsigned long long r = 0, c = 0;
   int32_t b = 1;
   size_t written = 0;
-  get(layout, 4, &r, sizeof(r), &written);
-  get(layout, 5, &c, sizeof(c), &written);
+  bool known = false;
+  {
+    std::lock_guard<std::mutex> g(g_layout_mu);
+    auto it = g_layout_dims.find(layout);
+    if (it != g_layout_dims.end()) {
+      r = it->second.first;
+      c = it->second.second;
+      known = true;
+    }
+  }
+  if (!known) {
+    get(layout, 4, &r, sizeof(r), &written);
+    get(layout, 5, &c, sizeof(c), &written);
+  }
   get(layout, 0, &b, sizeof(b), &written);
   *rows = (long long)r;
   *cols = (long long)c;

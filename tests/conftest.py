@@ -1,6 +1,23 @@
 import os
+import tempfile
 
 import pytest
+
+
+def _shorten_temp_root():
+    """AF_UNIX socket paths are capped at ~107 bytes, and the tests put their
+    IPC sockets under tmp_path / tempfile dirs (<root>/pytest-of-U/pytest-N/
+    <test>/ipc/<job>/ipc.sock is already ~90 bytes past the root). A deeply
+    nested TMPDIR overflows that, so fall back to /tmp when the configured
+    temp root is long. Set through TMPDIR so spawned agents/workers agree."""
+    if len(tempfile.gettempdir()) <= 16:
+        return
+    if os.path.isdir("/tmp") and os.access("/tmp", os.W_OK | os.X_OK):
+        os.environ["TMPDIR"] = "/tmp"
+        tempfile.tempdir = None  # re-read TMPDIR on next gettempdir()
+
+
+_shorten_temp_root()
 
 
 def pytest_configure(config):

@@ -29,12 +29,23 @@ def test_bench_default_contract(tmp_path):
                ELASTIC_JOB_NAME=f"bench{os.getpid()}")
     out = subprocess.run(
         [sys.executable, "bench.py", "--model", "tiny", "--steps", "4",
-         "--warmup", "1", "--seq", "64", "--ckpt-interval", "2"],
+         "--warmup", "1", "--seq", "64", "--ckpt-interval", "2",
+         "--dump-outputs", str(tmp_path / "dump")],
         cwd=ROOT, env=env, capture_output=True, text=True, timeout=300,
     )
     assert out.returncode == 0, out.stderr[-3000:]
     r = _parse_bench(out.stdout)
     assert REQUIRED_KEYS <= set(r)
+    # --dump-outputs: the last timed step's loss and a parameter sample
+    import numpy as np
+
+    loss = np.load(tmp_path / "dump" / "loss.npy")
+    params = np.load(tmp_path / "dump" / "params_sample.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,)
+    assert float(loss[0]) == pytest.approx(r["config"]["final_loss"], abs=1e-3)
+    assert params.dtype == np.float32 and params.size > 0
+    assert np.isfinite(params).all()
+    assert loss.nbytes + params.nbytes <= 64 << 20
     assert r["n_gpus"] == 1 and r["steps"] == 4 and r["warmup"] == 1
     assert r["higher_is_better"] is True and r["scaling"] == "weak"
     assert r["data"] == "synthetic"
@@ -55,7 +66,7 @@ def test_bench_under_torchrun(tmp_path):
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29743", "bench.py", "--gpus", "2", "--model",
          "tiny", "--steps", "4", "--warmup", "1", "--seq", "64",
-         "--ckpt-interval", "2"],
+         "--ckpt-interval", "2", "--full"],
         cwd=ROOT, env=env, capture_output=True, text=True, timeout=360,
     )
     assert out.returncode == 0, out.stderr[-3000:]

@@ -12,6 +12,12 @@ from tests.test_elastic_e2e import _read_progress, _run_cli
 pytestmark = pytest.mark.gpu
 
 
+def _job_name():
+    import uuid
+
+    return f"e2eg{uuid.uuid4().hex[:6]}"
+
+
 @pytest.mark.timeout(540)
 def test_nanogpt_rccl_clean_run_gpu(tmp_path):
     proc, progress, ckpt_dir = _run_cli(tmp_path, steps=8, ckpt_interval=4,
@@ -55,9 +61,16 @@ def test_nanogpt_hiptimer_metrics_gpu(tmp_path):
 
     from dlrover_amd import xpu_timer
 
+    # own job name: only this run's metrics dir is read, never another
+    # job's (or another user's) leftovers under the same parent
+    job = _job_name()
     proc, progress, ckpt_dir = _run_cli(
         tmp_path, steps=6, ckpt_interval=3, nproc=1,
-        extra_env={"DLROVER_HIPTIMER": "1", "HIPTIMER_DUMP_INTERVAL": "1"},
+        # HIPTIMER_SAMPLE=1 times every launch: with the default 1-in-32
+        # sampling a 6-step tiny model may never have a GEMM land on a
+        # sampled slot, and per-shape rows only exist for timed GEMMs
+        extra_env={"DLROVER_HIPTIMER": "1", "HIPTIMER_DUMP_INTERVAL": "1",
+                   "HIPTIMER_SAMPLE": "1", "ELASTIC_JOB_NAME": job},
     )
     assert proc.returncode == 0, (
         f"stdout:\n{proc.stdout[-3000:]}\nstderr:\n{proc.stderr[-5000:]}"
@@ -70,7 +83,7 @@ def test_nanogpt_hiptimer_metrics_gpu(tmp_path):
     deadline = time.time() + 20
     last = {}
     while time.time() < deadline:
-        candidates = glob.glob("/tmp/hiptimer_*/hiptimer_0.prom")
+        candidates = glob.glob(f"/tmp/hiptimer_{job}/hiptimer_0.prom")
         for path in sorted(candidates, key=os.path.getmtime, reverse=True):
             m = xpu_timer.parse_metrics_file(path)
             last = m or last
@@ -100,9 +113,11 @@ def test_hiptimer_timeline_dump_gpu(tmp_path):
     import os
     import time
 
+    job = _job_name()
     proc, progress, ckpt_dir = _run_cli(
         tmp_path, steps=25, ckpt_interval=30, nproc=1,
         extra_env={
+            "ELASTIC_JOB_NAME": job,
             "DLROVER_HIPTIMER": "1",
             "HIPTIMER_DUMP_INTERVAL": "1",
             "DLROVER_TEST_TIMELINE_FLAG": "1",
@@ -114,7 +129,7 @@ def test_hiptimer_timeline_dump_gpu(tmp_path):
     # DLROVER_TEST_TIMELINE_FLAG is set; find the dumped timeline
     deadline = time.time() + 15
     while time.time() < deadline:
-        for path in glob.glob("/tmp/hiptimer_*/timeline_*.json"):
+        for path in glob.glob(f"/tmp/hiptimer_{job}/timeline_*.json"):
             data = json.load(open(path))
             evs = data.get("traceEvents", [])
             if len(evs) > 20:
