@@ -14,7 +14,9 @@ from dlrover_amd.ops.api import (  # noqa: F401
     causal_softmax,
     flash_attention,
     cross_entropy_loss,
+    fused_adamw_multi_step,
     fused_adamw_step,
+    grad_sq_norm,
     hip_ops,
     hip_ops_available,
     rmsnorm,

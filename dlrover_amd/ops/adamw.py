@@ -15,13 +15,51 @@ Megatron/Apex (BASELINE.json north star). Design:
 State-dict format is torch-optimizer-compatible (state[param] has step /
 exp_avg / exp_avg_sq / master_param) so flash checkpoint handles it like any
 optimizer.
+
+Opt-in batched path (``multi_tensor=True`` and/or ``max_grad_norm=...``):
+  - the update runs as a few multi-tensor launches instead of one launch per
+    parameter (ops/csrc/multi_tensor.hip);
+  - with ``max_grad_norm`` the global gradient norm is computed on the device
+    from all local gradients (two kernels, no atomics), optionally
+    all-reduced, and the clip coefficient
+    ``min(1, max_norm / (norm + 1e-6))`` — the definition of
+    ``torch.nn.utils.clip_grad_norm_`` — is applied inside the update
+    kernel. Gradients are read, never rewritten; there is no host sync
+    anywhere in the step. ``opt.last_grad_norm`` is a 0-dim fp32 device
+    tensor with the pre-clip global norm; reading it is the caller's sync;
+  - a non-finite norm (inf/NaN gradient) with ``skip_nonfinite=True`` makes
+    the update kernel return without storing: master weights, both moments
+    and the bf16 weights stay bit-identical. The host cannot see that
+    without a sync, so ``state["step"]`` still advances on a skipped step and
+    bias correction drifts by one step per skip — the same approximation the
+    graph path already makes. Skipping needs the norm, so it is only active
+    together with ``max_grad_norm``.
+
+Which ranks the norm is summed over: an explicit ``grad_norm_group`` always
+wins. Without one, DTensor parameters (FSDP2) are reduced over their mesh's
+group — all parameters must share one 1-D mesh and be ``Shard``-placed,
+anything else raises NotImplementedError; plain tensors (single process, DDP
+replicas) are not reduced. The TP/PP stack in ``dlrover_amd/parallel`` is out
+of scope: it must pass ``grad_norm_group`` itself, and parameters replicated
+across that group would be counted once per rank.
+
+The new arguments live on the optimizer object, not in ``param_groups``, so
+checkpoints keep their format.
 """
 
+import logging
 from typing import Iterable, Optional
 
 import torch
 
-from dlrover_amd.ops.api import fused_adamw_step
+from dlrover_amd.ops.api import (
+    fused_adamw_multi_step,
+    fused_adamw_step,
+    grad_sq_norm,
+    grad_sq_norm_slots,
+)
+
+logger = logging.getLogger(__name__)
 
 try:
     from torch.distributed.tensor import DTensor
@@ -46,13 +84,32 @@ class FusedAdamW(torch.optim.Optimizer):
         eps: float = 1e-8,
         weight_decay: float = 0.1,
         capture_graph: bool = False,
+        max_grad_norm: Optional[float] = None,
+        multi_tensor: bool = False,
+        skip_nonfinite: bool = True,
+        grad_norm_group=None,
     ):
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._capture_graph = capture_graph and torch.cuda.is_available()
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._graph_ptrs = None
         self._lr_at_capture = None
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
+        self.grad_norm_group = grad_norm_group
+        self._batched = multi_tensor or max_grad_norm is not None
+        # 0-dim fp32 tensor on the params' device: global pre-clip norm of
+        # the last step (None until a clipped step has run)
+        self.last_grad_norm: Optional[torch.Tensor] = None
+        self._ws_key = None
+        self._ws_partials = None
+        self._ws_norm_sq = None
+        self._span_elems = 0  # 0 = automatic
+        self._reduce_group_cache = None
+        self._warned_no_capture = False
 
     def _init_state(self, p: torch.Tensor):
         state = self.state[p]
@@ -91,6 +148,134 @@ class FusedAdamW(torch.optim.Optimizer):
                     # fp32 params: master IS the param storage
                     p_data.copy_(state["master_param"])
 
+    def _norm_reduce_group(self, params):
+        """Process group the squared norm is summed over, or None."""
+        if self.grad_norm_group is not None:
+            return self.grad_norm_group
+        if self._reduce_group_cache is not None:
+            return self._reduce_group_cache[0]
+        dts = [p for p in params if DTensor and isinstance(p, DTensor)]
+        group = None
+        if dts:
+            mesh = dts[0].device_mesh
+            ok = len(dts) == len(params) and mesh.ndim == 1
+            for p in dts:
+                ok = ok and p.device_mesh == mesh
+                ok = ok and all(pl.is_shard() for pl in p.placements)
+            if not ok:
+                raise NotImplementedError(
+                    "FusedAdamW(max_grad_norm=...): the global gradient norm "
+                    "is only derived automatically when every parameter is a "
+                    "DTensor sharded (Shard placement) over one common 1-D "
+                    "device mesh, or none is a DTensor. Pass grad_norm_group "
+                    "explicitly for any other layout."
+                )
+            group = mesh.get_group()
+        self._reduce_group_cache = (group,)
+        return group
+
+    def _global_norm_sq(self, grads, params):
+        dev = grads[0].device
+        key = (tuple((g.numel(), g.dtype) for g in grads), dev, self._span_elems)
+        if key != self._ws_key:
+            # persistent workspace: reallocated only when the set of
+            # gradient sizes changes
+            slots = grad_sq_norm_slots(grads, self._span_elems)
+            self._ws_partials = torch.empty(
+                max(slots, 1), device=dev, dtype=torch.float32
+            )
+            self._ws_norm_sq = torch.zeros(1, device=dev, dtype=torch.float32)
+            self.last_grad_norm = torch.zeros((), device=dev, dtype=torch.float32)
+            self._ws_key = key
+        grad_sq_norm(
+            grads,
+            out=self._ws_norm_sq,
+            partials=self._ws_partials,
+            span_elems=self._span_elems,
+        )
+        group = self._norm_reduce_group(params)
+        if group is not None:
+            torch.distributed.all_reduce(self._ws_norm_sq, group=group)
+        torch.sqrt(self._ws_norm_sq[0], out=self.last_grad_norm)
+        return self._ws_norm_sq
+
+    def _mt_step(self):
+        """Batched path: [global norm ->] one multi-tensor update per
+        (param group, gradient dtype). No host sync."""
+        if self.max_grad_norm is not None:
+            # refuse an unsupported layout before any state is touched
+            self._norm_reduce_group(
+                [p for g in self.param_groups for p in g["params"]
+                 if p.grad is not None]
+            )
+        batches, grads, params, fp32_copies = [], [], [], []
+        for group in self.param_groups:
+            by_dtype = {}
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                state = self.state[p]
+                if "master_param" not in state:
+                    self._init_state(p)
+                state["step"] += 1
+                g = _local(p.grad).contiguous()
+                p_data = _local(p.data)
+                is_bf16 = p.dtype == torch.bfloat16
+                b = by_dtype.setdefault(g.dtype, ([], [], [], [], [], []))
+                b[0].append(state["master_param"])
+                b[1].append(g)
+                b[2].append(state["exp_avg"])
+                b[3].append(state["exp_avg_sq"])
+                b[4].append(p_data if is_bf16 else None)
+                b[5].append(state["step"])
+                grads.append(g)
+                params.append(p)
+                if not is_bf16:
+                    fp32_copies.append((p_data, state["master_param"]))
+            batches.extend((group, b) for b in by_dtype.values())
+        if not grads:
+            return
+        norm_sq = None
+        if self.max_grad_norm is not None:
+            norm_sq = self._global_norm_sq(grads, params)
+        for group, b in batches:
+            n = len(b[0])
+            fused_adamw_multi_step(
+                b[0], b[1], b[2], b[3], b[4],
+                [group["lr"]] * n,
+                [group["weight_decay"]] * n,
+                b[5],
+                group["betas"][0],
+                group["betas"][1],
+                group["eps"],
+                1.0,
+                norm_sq,
+                self.max_grad_norm if norm_sq is not None else float("inf"),
+                self.skip_nonfinite,
+                self._span_elems,
+            )
+        for p_data, master in fp32_copies:
+            # fp32 params: master IS the param storage
+            p_data.copy_(master)
+
+    def _can_capture(self):
+        if not self._capture_graph:
+            return False
+        if not self._batched or self.max_grad_norm is None:
+            return True
+        params = [
+            p for g in self.param_groups for p in g["params"] if p.grad is not None
+        ]
+        if self._norm_reduce_group(params) is None:
+            return True
+        if not self._warned_no_capture:
+            logger.warning(
+                "FusedAdamW: capture_graph is ignored while the gradient "
+                "norm is all-reduced over a process group; running eagerly"
+            )
+            self._warned_no_capture = True
+        return False
+
     def _grad_ptrs(self):
         return tuple(
             p.grad.data_ptr()
@@ -105,8 +290,9 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if not self._capture_graph:
-            self._one_step()
+        one_step = self._mt_step if self._batched else self._one_step
+        if not self._can_capture():
+            one_step()
             return loss
 
         ptrs = self._grad_ptrs()
@@ -124,7 +310,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 if p.grad is not None
             )
             if min_step < 100:
-                self._one_step()
+                one_step()
                 return loss
             torch.cuda.synchronize()
             self._graph = torch.cuda.CUDAGraph()
@@ -132,8 +318,10 @@ class FusedAdamW(torch.optim.Optimizer):
             # step counters bumped inside _one_step() then describe work
             # that has not run yet. Replay immediately (capture-then-replay)
             # so the capture iteration's gradients are actually applied.
+            # the batched path captures the same way: the clip coefficient
+            # is computed on the device, so every replay recomputes it
             with torch.cuda.graph(self._graph):
-                self._one_step()
+                one_step()
             self._graph.replay()
             self._graph_ptrs = ptrs
             self._lr_at_capture = lr

@@ -457,3 +457,131 @@ def fused_adamw_step(
     )
     if param_bf16 is not None:
         param_bf16.copy_(param_f32.to(param_bf16.dtype))
+
+
+# ---------------------------------------------------------------------------
+# multi-tensor ops: global gradient norm + batched AdamW
+# ---------------------------------------------------------------------------
+
+
+def grad_sq_norm_slots(tensors, span_elems: int = 0) -> int:
+    """How many fp32 partial slots ``grad_sq_norm`` needs for this tensor
+    list at this span (0 = automatic). The CPU reference needs none."""
+    tensors = list(tensors)
+    if _use_hip(*tensors):
+        return int(hip_ops().multi_tensor_num_partials(tensors, span_elems))
+    return 0
+
+
+def grad_sq_norm(
+    tensors,
+    out: Optional[torch.Tensor] = None,
+    partials: Optional[torch.Tensor] = None,
+    span_elems: int = 0,
+) -> torch.Tensor:
+    """Sum of squares over every element of every tensor (bf16 or fp32,
+    contiguous, any element offset) into ``out[0]`` (fp32). No host sync.
+
+    GPU: two kernels, no atomics — bitwise reproducible. ``partials`` is the
+    caller-owned fp32 workspace of ``grad_sq_norm_slots`` elements and
+    ``out`` a caller-owned fp32 tensor; both are allocated here when omitted
+    (pass them to stay allocation-free, e.g. under graph capture)."""
+    tensors = list(tensors)
+    if _use_hip(*tensors, out):
+        dev = next(t.device for t in tensors + [out] if t is not None and t.is_cuda)
+        if out is None:
+            out = torch.empty(1, device=dev, dtype=torch.float32)
+        if partials is None:
+            n = hip_ops().multi_tensor_num_partials(tensors, span_elems)
+            partials = torch.empty(max(int(n), 1), device=dev, dtype=torch.float32)
+        hip_ops().multi_tensor_sq_norm(tensors, partials, out, span_elems)
+        return out
+    # CPU reference
+    total = torch.zeros((), dtype=torch.float64)
+    for t in tensors:
+        if t.numel():
+            total = total + t.detach().float().pow(2).sum(dtype=torch.float64)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32)
+    out.view(-1)[0] = total.float()
+    return out
+
+
+def fused_adamw_multi_step(
+    masters,
+    grads,
+    exp_avgs,
+    exp_avg_sqs,
+    params_bf16,
+    lrs,
+    weight_decays,
+    steps,
+    beta1: float,
+    beta2: float,
+    eps: float,
+    grad_scale: float = 1.0,
+    norm_sq: Optional[torch.Tensor] = None,
+    max_norm: float = float("inf"),
+    skip_nonfinite: bool = True,
+    span_elems: int = 0,
+):
+    """AdamW over a list of tensors in a few batched launches.
+
+    Per-tensor: master/grad/moments, optional bf16 working copy (``None``
+    entries, or ``params_bf16=None`` for none at all), lr, weight decay and
+    step. Per call: betas, eps, one gradient dtype.
+
+    With ``norm_sq`` (fp32 tensor holding the global squared gradient norm)
+    every gradient is additionally multiplied by
+    ``min(1, max_norm / (sqrt(norm_sq) + 1e-6))`` — torch's
+    ``clip_grad_norm_`` coefficient — computed on the device. If ``norm_sq``
+    is not finite and ``skip_nonfinite`` is set nothing is written at all."""
+    masters = list(masters)
+    if not masters:
+        return
+    if params_bf16 is None:
+        params_bf16 = [None] * len(masters)
+    if masters[0].is_cuda:
+        hip_ops().multi_tensor_adamw(
+            masters,
+            [g.contiguous() for g in grads],
+            list(exp_avgs),
+            list(exp_avg_sqs),
+            list(params_bf16),
+            [float(x) for x in lrs],
+            [float(x) for x in weight_decays],
+            [int(x) for x in steps],
+            beta1,
+            beta2,
+            eps,
+            grad_scale,
+            norm_sq,
+            max_norm,
+            skip_nonfinite,
+            span_elems,
+        )
+        return
+    # CPU reference: the per-tensor reference with the clip folded into the
+    # gradient scale
+    scale = grad_scale
+    if norm_sq is not None:
+        nsq = norm_sq.detach().reshape(-1)[0].float()
+        if skip_nonfinite and not bool(torch.isfinite(nsq)):
+            return
+        coef = torch.clamp(max_norm / (nsq.sqrt() + 1e-6), max=1.0)
+        scale = coef * grad_scale
+    for i, master in enumerate(masters):
+        fused_adamw_step(
+            master,
+            grads[i],
+            exp_avgs[i],
+            exp_avg_sqs[i],
+            params_bf16[i],
+            lrs[i],
+            beta1,
+            beta2,
+            eps,
+            weight_decays[i],
+            steps[i],
+            scale,
+        )

@@ -7,6 +7,7 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include <tuple>
+#include <vector>
 
 extern "C" {
 void rmsnorm_fwd_launch(const void*, const void*, void*, void*, int, int,
@@ -58,6 +59,16 @@ void fa_bwd_dkv_launch(const void*, const void*, const void*, const void*,
                        const void*, const void*, void*, void*, int, int, int,
                        int, float, const long long*, void*);
 void f32_to_bf16_launch(const void*, void*, long long, void*);
+int mt_max_tensors();
+long long mt_auto_span(long long);
+long long mt_num_blocks(int, const long long*, long long);
+void mt_sqnorm_launch(int, const void* const*, const long long*, const int*,
+                      long long, float*, float*, void*);
+void mt_adamw_launch(int, void* const*, const void* const*, void* const*,
+                     void* const*, void* const*, const long long*,
+                     const float*, const float*, const int*, int, float,
+                     float, float, float, const float*, float, int, long long,
+                     void*);
 }
 
 namespace {
@@ -476,6 +487,134 @@ at::Tensor cross_entropy_fwd_bwd(at::Tensor& logits, const at::Tensor& targets,
   return losses;
 }
 
+// ---- multi-tensor ops (multi_tensor.hip) ---------------------------------
+// span_elems == 0 picks the span from the list's total size; any other value
+// must be a multiple of 8 and is used as given.
+long long mt_span(const std::vector<long long>& numel, int64_t span_elems) {
+  TORCH_CHECK(span_elems >= 0 && span_elems % 8 == 0,
+              "span_elems must be 0 (automatic) or a positive multiple of 8");
+  if (span_elems > 0) return span_elems;
+  long long total = 0;
+  for (long long n : numel) total += n;
+  return mt_auto_span(total);
+}
+
+std::vector<long long> mt_numels(const std::vector<at::Tensor>& ts) {
+  std::vector<long long> numel;
+  numel.reserve(ts.size());
+  for (const auto& t : ts) numel.push_back((long long)t.numel());
+  return numel;
+}
+
+int64_t multi_tensor_num_partials(const std::vector<at::Tensor>& tensors,
+                                  int64_t span_elems) {
+  const auto numel = mt_numels(tensors);
+  return mt_num_blocks((int)numel.size(), numel.data(),
+                       mt_span(numel, span_elems));
+}
+
+void multi_tensor_sq_norm(const std::vector<at::Tensor>& tensors,
+                          at::Tensor& partials, at::Tensor& out,
+                          int64_t span_elems) {
+  const auto numel = mt_numels(tensors);
+  const long long span = mt_span(numel, span_elems);
+  const int n = (int)tensors.size();
+  std::vector<const void*> ptrs(n);
+  std::vector<int> is_bf16(n);
+  for (int i = 0; i < n; ++i) {
+    const auto& t = tensors[i];
+    TORCH_CHECK(t.is_cuda(), "sq_norm: tensors must be on GPU");
+    TORCH_CHECK(t.numel() == 0 || t.is_contiguous(),
+                "sq_norm: tensors must be contiguous");
+    is_bf16[i] = t.scalar_type() == at::kBFloat16;
+    TORCH_CHECK(is_bf16[i] || t.scalar_type() == at::kFloat,
+                "sq_norm: tensors must be bf16 or fp32");
+    ptrs[i] = t.numel() ? t.data_ptr() : nullptr;
+  }
+  const long long need = mt_num_blocks(n, numel.data(), span);
+  TORCH_CHECK(need < (1LL << 31), "sq_norm: too many spans");
+  TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
+                  partials.scalar_type() == at::kFloat &&
+                  partials.numel() >= need,
+              "sq_norm: partials must be contiguous fp32 on GPU with at "
+              "least ", need, " elements");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
+                  out.numel() >= 1,
+              "sq_norm: out must be fp32 on GPU");
+  mt_sqnorm_launch(n, ptrs.data(), numel.data(), is_bf16.data(), span,
+                   (float*)partials.data_ptr(), (float*)out.data_ptr(),
+                   cur_stream());
+}
+
+void multi_tensor_adamw(
+    const std::vector<at::Tensor>& masters,
+    const std::vector<at::Tensor>& grads,
+    const std::vector<at::Tensor>& exp_avgs,
+    const std::vector<at::Tensor>& exp_avg_sqs,
+    c10::optional<std::vector<c10::optional<at::Tensor>>> params_bf16,
+    const std::vector<double>& lrs, const std::vector<double>& weight_decays,
+    const std::vector<int64_t>& steps, double beta1, double beta2, double eps,
+    double grad_scale, c10::optional<at::Tensor> norm_sq, double max_norm,
+    bool skip_nonfinite, int64_t span_elems) {
+  const size_t n = masters.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n &&
+                  exp_avg_sqs.size() == n && lrs.size() == n &&
+                  weight_decays.size() == n && steps.size() == n &&
+                  (!params_bf16.has_value() || params_bf16->size() == n),
+              "multi_tensor_adamw: list lengths differ");
+  if (n == 0) return;
+  const auto numel = mt_numels(masters);
+  const long long span = mt_span(numel, span_elems);
+  const bool gbf16 = grads[0].scalar_type() == at::kBFloat16;
+  std::vector<void*> pm(n), pe(n), pv(n), pb(n, nullptr);
+  std::vector<const void*> pg(n);
+  std::vector<float> lr(n), wd(n);
+  std::vector<int> st(n);
+  for (size_t i = 0; i < n; ++i) {
+    const auto& p = masters[i];
+    const auto& g = grads[i];
+    auto check_f32 = [&](const at::Tensor& t, const char* name) {
+      TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                      t.is_contiguous() && t.numel() == p.numel(),
+                  name, " must be contiguous fp32 on GPU, numel matching");
+    };
+    check_f32(p, "master param");
+    check_f32(exp_avgs[i], "exp_avg");
+    check_f32(exp_avg_sqs[i], "exp_avg_sq");
+    TORCH_CHECK(g.is_cuda() && g.is_contiguous(), "grad must be GPU");
+    TORCH_CHECK(g.numel() == p.numel(), "grad/param numel mismatch");
+    TORCH_CHECK(g.scalar_type() == (gbf16 ? at::kBFloat16 : at::kFloat),
+                "grads of one call must all be bf16 or all be fp32");
+    pm[i] = p.data_ptr();
+    pg[i] = g.data_ptr();
+    pe[i] = exp_avgs[i].data_ptr();
+    pv[i] = exp_avg_sqs[i].data_ptr();
+    if (params_bf16.has_value() && (*params_bf16)[i].has_value()) {
+      const auto& b = *(*params_bf16)[i];
+      check_bf16(b, "param_bf16");
+      TORCH_CHECK(b.numel() == p.numel(), "param_bf16 numel mismatch");
+      pb[i] = b.data_ptr();
+    }
+    lr[i] = (float)lrs[i];
+    wd[i] = (float)weight_decays[i];
+    st[i] = (int)steps[i];
+  }
+  const float* nsq = nullptr;
+  if (norm_sq.has_value()) {
+    TORCH_CHECK(norm_sq->is_cuda() && norm_sq->scalar_type() == at::kFloat &&
+                    norm_sq->numel() >= 1,
+                "norm_sq must be fp32 on GPU");
+    nsq = (const float*)norm_sq->data_ptr();
+  }
+  TORCH_CHECK(mt_num_blocks((int)n, numel.data(), span) < (1LL << 31),
+              "multi_tensor_adamw: too many spans");
+  mt_adamw_launch((int)n, pm.data(), pg.data(), pe.data(), pv.data(),
+                  pb.data(), numel.data(), lr.data(), wd.data(), st.data(),
+                  gbf16 ? 1 : 0, (float)beta1, (float)beta2, (float)eps,
+                  (float)grad_scale, nsq, (float)max_norm,
+                  skip_nonfinite ? 1 : 0, span, cur_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -520,4 +659,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flash attention forward (bf16, causal, GQA, D=128) -> (out, lse)");
   m.def("flash_attn_bwd", &flash_attn_bwd,
         "flash attention backward -> (dq, dk, dv)");
+  m.attr("MT_MAX_TENSORS") = mt_max_tensors();
+  m.def("multi_tensor_num_partials", &multi_tensor_num_partials,
+        "partial slots multi_tensor_sq_norm needs for a tensor list",
+        py::arg("tensors"), py::arg("span_elems") = 0);
+  m.def("multi_tensor_sq_norm", &multi_tensor_sq_norm,
+        "sum of squares over a tensor list -> out[0] (fp32, no atomics)",
+        py::arg("tensors"), py::arg("partials"), py::arg("out"),
+        py::arg("span_elems") = 0);
+  m.def("multi_tensor_adamw", &multi_tensor_adamw,
+        "batched fused AdamW with an optional device-side clip coefficient",
+        py::arg("masters"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_sqs"), py::arg("params_bf16"), py::arg("lrs"),
+        py::arg("weight_decays"), py::arg("steps"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("grad_scale"),
+        py::arg("norm_sq"), py::arg("max_norm"), py::arg("skip_nonfinite"),
+        py::arg("span_elems") = 0);
 }

@@ -33,6 +33,9 @@ def main():
     p.add_argument("--ckpt-dir", default="/tmp/dlrover_amd_ckpt/llama")
     p.add_argument("--progress-file", default="")
     p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--grad-clip", type=float, default=0.0,
+                   help="clip the global gradient norm at this value inside "
+                        "the fused optimizer (0 = off)")
     p.add_argument("--act-ckpt", action="store_true",
                    help="recompute transformer blocks in backward")
     args = p.parse_args()
@@ -80,7 +83,8 @@ def main():
         for blk in model.blocks:
             fully_shard(blk)
         fully_shard(model)
-    opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=0.1)
+    clip_kw = {"max_grad_norm": args.grad_clip} if args.grad_clip > 0 else {}
+    opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=0.1, **clip_kw)
     trainer = ElasticTrainer(model)
 
     cp = FsdpShardCheckpointer(args.ckpt_dir, model, opt)
@@ -105,6 +109,11 @@ def main():
             loss.backward()
         opt.step()
         opt.zero_grad()
+        extra = {}
+        if args.grad_clip > 0 and args.progress_file and rank == 0:
+            # reading the device-side norm is this script's sync, next to
+            # the loss.item() the record already pays for
+            extra["grad_norm"] = round(float(opt.last_grad_norm), 4)
         if step % args.ckpt_interval == 0:
             blocking = cp.save_checkpoint(step, storage_type=StorageType.DISK)
             if rank == 0:
@@ -119,6 +128,7 @@ def main():
                     "incarnation": incarnation, "resumed_from": start_step,
                     "world": dist.get_world_size(),
                     "device": str(device),
+                    **extra,
                 }) + "\n")
         if kill_at and step == kill_at and incarnation == 0 and rank == 0:
             print(f"[train] injecting SIGKILL at step {step}", flush=True)

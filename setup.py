@@ -23,6 +23,7 @@ sources = [
     os.path.join(CSRC, "rope.hip"),
     os.path.join(CSRC, "swiglu.hip"),
     os.path.join(CSRC, "adamw.hip"),
+    os.path.join(CSRC, "multi_tensor.hip"),
     os.path.join(CSRC, "softmax.hip"),
     os.path.join(CSRC, "cross_entropy.hip"),
     os.path.join(CSRC, "mfma_probe.hip"),
