@@ -20,10 +20,20 @@ import torch
 import torch.nn as nn
 
 from dlrover_amd.models.llama import LlamaConfig, RMSNorm
-from dlrover_amd.ops import causal_softmax, cross_entropy_loss, rope_rotate, swiglu
+from dlrover_amd.ops import (
+    causal_softmax,
+    cross_entropy_loss,
+    rope_rotate,
+    swiglu,
+    vocab_parallel_cross_entropy,
+)
 from dlrover_amd.ops.api import build_rope_cache
 from dlrover_amd.parallel.pgroups import ParallelGroups
-from dlrover_amd.parallel.tp import ColumnParallelLinear, RowParallelLinear
+from dlrover_amd.parallel.tp import (
+    ColumnParallelLinear,
+    RowParallelLinear,
+    VocabParallelEmbedding,
+)
 
 
 class ParallelAttention(nn.Module):
@@ -118,30 +128,51 @@ def stage_layer_range(n_layers: int, pp_rank: int, pp: int):
 
 
 class LlamaStage(nn.Module):
-    """One pipeline stage: [embed]? + blocks[lo:hi] + [norm + lm_head]?."""
+    """One pipeline stage: [embed]? + blocks[lo:hi] + [norm + lm_head]?.
 
-    def __init__(self, cfg: LlamaConfig, groups: ParallelGroups):
+    ``vocab_parallel=True`` (effective at tp > 1) splits the vocabulary
+    dimension of ``embed`` and ``lm_head`` across the TP group instead of
+    replicating both matrices on every TP rank: the first stage holds a
+    ``VocabParallelEmbedding``, the last stage a column-parallel ``lm_head``
+    whose local ``[tokens, V/tp]`` logits feed ``vocab_parallel_cross_entropy``
+    directly — full-vocab logits are never formed when labels are given.
+    Without labels the last stage returns the logits all-gathered along the
+    vocab dimension; that path is forward-only (inference / evaluation), no
+    gradient flows through the gather."""
+
+    def __init__(self, cfg: LlamaConfig, groups: ParallelGroups,
+                 vocab_parallel: bool = False):
         super().__init__()
         self.cfg = cfg
         self.groups = groups
+        tp = groups.dims.tp
+        self.vocab_parallel = bool(vocab_parallel) and tp > 1
+        if self.vocab_parallel and cfg.vocab_size % tp:
+            raise ValueError(f"vocab_size {cfg.vocab_size} % tp {tp} != 0")
         lo, hi = stage_layer_range(cfg.n_layers, groups.pp_rank, groups.dims.pp)
         self.layer_range = (lo, hi)
-        self.embed = (
-            nn.Embedding(cfg.vocab_size, cfg.hidden_size)
-            if groups.is_first_stage
-            else None
-        )
+        self.embed = None
+        if groups.is_first_stage:
+            self.embed = (
+                VocabParallelEmbedding(cfg.vocab_size, cfg.hidden_size, tp,
+                                       groups.tp_rank, groups.tp_group)
+                if self.vocab_parallel
+                else nn.Embedding(cfg.vocab_size, cfg.hidden_size)
+            )
         self.blocks = nn.ModuleList(
             ParallelBlock(cfg, groups) for _ in range(hi - lo)
         )
         self.final_norm = (
             RMSNorm(cfg.hidden_size, cfg.norm_eps) if groups.is_last_stage else None
         )
-        self.lm_head = (
-            nn.Linear(cfg.hidden_size, cfg.vocab_size, bias=False)
-            if groups.is_last_stage
-            else None
-        )
+        self.lm_head = None
+        if groups.is_last_stage:
+            self.lm_head = (
+                ColumnParallelLinear(cfg.hidden_size, cfg.vocab_size, tp,
+                                     groups.tp_group)
+                if self.vocab_parallel
+                else nn.Linear(cfg.hidden_size, cfg.vocab_size, bias=False)
+            )
         cos, sin = build_rope_cache(cfg.max_seq_len, cfg.head_dim, cfg.rope_base)
         self.register_buffer("rope_cos", cos, persistent=False)
         self.register_buffer("rope_sin", sin, persistent=False)
@@ -157,7 +188,7 @@ class LlamaStage(nn.Module):
     def _init(m):
         if isinstance(m, (nn.Linear, ColumnParallelLinear, RowParallelLinear)):
             nn.init.normal_(m.weight, std=0.02)
-        elif isinstance(m, nn.Embedding):
+        elif isinstance(m, (nn.Embedding, VocabParallelEmbedding)):
             nn.init.normal_(m.weight, std=0.02)
 
     def forward(self, x, labels: Optional[torch.Tensor] = None):
@@ -172,8 +203,28 @@ class LlamaStage(nn.Module):
             return x
         x = self.final_norm(x)
         logits = self.lm_head(x)
+        if self.vocab_parallel:
+            return self._vocab_parallel_tail(logits, labels)
         if labels is None:
             return logits
         return cross_entropy_loss(
             logits.reshape(-1, self.cfg.vocab_size), labels.reshape(-1)
         )
+
+    def _vocab_parallel_tail(self, logits, labels):
+        """logits: this rank's [B, S, V/tp] columns of the lm_head output."""
+        tp, group = self.groups.dims.tp, self.groups.tp_group
+        vs = self.cfg.vocab_size // tp
+        if labels is not None:
+            return vocab_parallel_cross_entropy(
+                logits.reshape(-1, vs), labels.reshape(-1),
+                self.groups.tp_rank * vs, group,
+            )
+        # forward-only: gather the shards back into full-vocab logits
+        import torch.distributed as dist
+
+        shard = logits.detach().reshape(-1, vs).contiguous()
+        gathered = shard.new_empty((tp * shard.shape[0], vs))
+        dist.all_gather_into_tensor(gathered, shard, group=group)
+        full = gathered.view(tp, -1, vs).transpose(0, 1)  # [tokens, tp, vs]
+        return full.reshape(*logits.shape[:-1], tp * vs)

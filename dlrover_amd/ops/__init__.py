@@ -12,6 +12,8 @@ Loading policy (the framework's hot path must actually run native code):
 from dlrover_amd.ops.api import (  # noqa: F401
     ExtensionMissingError,
     causal_softmax,
+    ce_shard_finish,
+    ce_shard_stats,
     flash_attention,
     cross_entropy_loss,
     fused_adamw_multi_step,
@@ -23,5 +25,6 @@ from dlrover_amd.ops.api import (  # noqa: F401
     rmsnorm_add,
     rope_rotate,
     swiglu,
+    vocab_parallel_cross_entropy,
 )
 from dlrover_amd.ops.adamw import FusedAdamW  # noqa: F401

@@ -414,6 +414,146 @@ def cross_entropy_loss(
     return _CrossEntropy.apply(logits, targets, ignore_index)
 
 
+# ---------------------------------------------------------------------------
+# vocab-parallel cross-entropy: the softmax split around one all-gather
+# ---------------------------------------------------------------------------
+
+
+def ce_shard_stats(
+    logits_shard: torch.Tensor,
+    targets: torch.Tensor,
+    vocab_start: int,
+    ignore_index: int = -100,
+) -> torch.Tensor:
+    """Stage 1 of the vocab-parallel CE on one ``[N, Vs]`` column shard of
+    the logits: fp32 ``stats[N, 3] = (m, s, t)`` per row — the shard max,
+    ``sum exp(x - m)`` over the shard, and the target's logit when
+    ``vocab_start <= target < vocab_start + Vs`` (else 0). ``targets`` hold
+    GLOBAL vocabulary ids. Every row gets defined values, ignored rows too
+    (the buffer goes through a collective). GPU: one read of the shard."""
+    vs = logits_shard.shape[-1]
+    if _use_hip(logits_shard):
+        return hip_ops().ce_shard_stats(
+            logits_shard.view(-1, vs), targets.reshape(-1).int(), vocab_start,
+            ignore_index,
+        )
+    x = logits_shard.detach().reshape(-1, vs).float()
+    t = targets.reshape(-1).long()
+    m = x.amax(-1)
+    s = torch.exp(x - m[:, None]).sum(-1)
+    local = t - vocab_start
+    owns = (t != ignore_index) & (local >= 0) & (local < vs)
+    # never index with an out-of-shard target: clamp it to column 0 first
+    picked = x.gather(1, torch.where(owns, local, 0)[:, None]).squeeze(1)
+    return torch.stack([m, s, torch.where(owns, picked, 0.0)], dim=1)
+
+
+def ce_shard_finish(
+    logits_shard: torch.Tensor,
+    targets: torch.Tensor,
+    vocab_start: int,
+    stats_all: torch.Tensor,
+    grad_scale: float,
+    ignore_index: int = -100,
+    compute_grad: bool = True,
+) -> torch.Tensor:
+    """Stage 2: combine ``stats_all[tp, N, 3]`` (every shard's stats in rank
+    order) into the per-row loss and overwrite ``logits_shard`` in place with
+    ``(softmax - onehot) * grad_scale`` for this shard's columns. The combine
+    runs in rank order r = 0..tp-1, so every shard that is handed the same
+    ``stats_all`` returns bitwise the same losses. Ignored rows: loss 0 and
+    zero gradients. The logits shard is consumed."""
+    vs = logits_shard.shape[-1]
+    if _use_hip(logits_shard):
+        return hip_ops().ce_shard_finish(
+            logits_shard.view(-1, vs), targets.reshape(-1).int(), vocab_start,
+            stats_all, grad_scale, ignore_index, compute_grad,
+        )
+    t = targets.reshape(-1).long()
+    n = t.numel()
+    sa = stats_all.reshape(-1, n, 3).float()
+    tp = sa.shape[0]
+    gm = sa[0, :, 0]
+    for r in range(1, tp):
+        gm = torch.maximum(gm, sa[r, :, 0])
+    gs = torch.zeros_like(gm)
+    gt = torch.zeros_like(gm)
+    for r in range(tp):
+        gs = gs + sa[r, :, 1] * torch.exp(sa[r, :, 0] - gm)
+        gt = gt + sa[r, :, 2]
+    lse = gm + torch.log(gs)
+    valid = t != ignore_index
+    losses = torch.where(valid, lse - gt, 0.0)
+    if compute_grad:
+        x = logits_shard.detach().reshape(-1, vs).float()
+        dl = torch.exp(x - lse[:, None])
+        local = t - vocab_start
+        owns = valid & (local >= 0) & (local < vs)
+        rows = owns.nonzero().squeeze(1)
+        dl[rows, local[rows]] -= 1.0
+        dl = dl * grad_scale
+        dl[~valid] = 0
+        with torch.no_grad():
+            logits_shard.copy_(dl.view_as(logits_shard))
+    return losses
+
+
+class _VocabParallelCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits_shard, targets, vocab_start, tp_group, ignore_index):
+        n_valid = int((targets != ignore_index).sum())
+        grad_scale = 1.0 / max(n_valid, 1)
+        if _use_hip(logits_shard):
+            work = logits_shard.contiguous()  # consumed, as cross_entropy_loss
+            tgt = targets.reshape(-1).int().contiguous()
+        else:
+            work = logits_shard.detach().float().clone()
+            tgt = targets.reshape(-1)
+        stats = ce_shard_stats(work, tgt, vocab_start, ignore_index)
+        if tp_group is None:  # tp degenerate (parallel/tp.py): no collective
+            stats_all = stats[None]
+        else:
+            import torch.distributed as dist
+
+            tp = dist.get_world_size(tp_group)
+            # gathered concatenated along dim 0 (the layout every backend
+            # accepts), which IS [tp, N, 3] in rank order
+            flat = stats.new_empty((tp * stats.shape[0], 3))
+            dist.all_gather_into_tensor(flat, stats, group=tp_group)
+            stats_all = flat.view(tp, stats.shape[0], 3)
+        losses = ce_shard_finish(
+            work, tgt, vocab_start, stats_all, grad_scale, ignore_index, True
+        )
+        # work now holds this shard's dlogits (pre-scaled)
+        ctx.save_for_backward(work.to(logits_shard.dtype).view_as(logits_shard))
+        return losses.sum() * grad_scale
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * dloss, None, None, None, None
+
+
+def vocab_parallel_cross_entropy(
+    logits_shard: torch.Tensor,
+    targets: torch.Tensor,
+    vocab_start: int,
+    tp_group=None,
+    ignore_index: int = -100,
+) -> torch.Tensor:
+    """Mean CE over non-ignored tokens when the vocabulary dimension is split
+    across a tensor-parallel group: ``logits_shard`` is this rank's
+    ``[tokens, V/tp]`` columns starting at global id ``vocab_start``,
+    ``targets`` hold global ids. One collective (an all-gather of the
+    ``[N, 3]`` row statistics) and two kernels; every rank combines the same
+    gathered buffer in the same order, so the loss is bitwise identical across
+    the group. ``tp_group=None`` is the degenerate single-shard case. The GPU
+    path consumes ``logits_shard`` (reused for dlogits)."""
+    return _VocabParallelCrossEntropy.apply(
+        logits_shard, targets, vocab_start, tp_group, ignore_index
+    )
+
+
 def fused_adamw_step(
     param_f32: torch.Tensor,
     grad: torch.Tensor,

@@ -31,6 +31,10 @@ void causal_softmax_bwd_launch(void*, const void*, long long, int, float,
                                void*);
 void cross_entropy_launch(void*, const void*, void*, long long, int, int,
                           float, int, void*);
+void ce_shard_stats_launch(const void*, const void*, void*, long long, int,
+                           int, int, void*);
+void ce_shard_finish_launch(void*, const void*, const void*, void*, long long,
+                            int, int, int, int, float, int, void*);
 void mfma16_probe_launch(const void*, const void*, void*, void*);
 void mfma32_probe_launch(const void*, const void*, void*, void*);
 void tr_b16_probe3_launch(void*, void*);
@@ -487,6 +491,61 @@ at::Tensor cross_entropy_fwd_bwd(at::Tensor& logits, const at::Tensor& targets,
   return losses;
 }
 
+// ---- vocab-parallel cross-entropy (vocab_parallel_ce.hip) ----------------
+// Validates one [N, Vs] logits shard and its N global-id targets; returns N.
+long long check_ce_shard(const at::Tensor& logits_shard,
+                         const at::Tensor& targets, int64_t vocab_start) {
+  check_bf16(logits_shard, "logits_shard");
+  TORCH_CHECK(logits_shard.dim() >= 1, "logits_shard must be [N, Vs]");
+  const int64_t vs = logits_shard.size(-1);
+  TORCH_CHECK(vs > 0 && vs % 8 == 0 && vs < (1LL << 31),
+              "shard width Vs must be a positive multiple of 8, got ", vs);
+  TORCH_CHECK(vocab_start >= 0 && vocab_start + vs < (1LL << 31),
+              "vocab_start out of int32 range");
+  TORCH_CHECK(targets.scalar_type() == at::kInt && targets.is_cuda() &&
+                  targets.is_contiguous(),
+              "targets must be contiguous int32 on GPU");
+  const long long n_rows = logits_shard.numel() / vs;
+  TORCH_CHECK(targets.numel() == n_rows, "one target per row");
+  return n_rows;
+}
+
+at::Tensor ce_shard_stats(const at::Tensor& logits_shard,
+                          const at::Tensor& targets, int64_t vocab_start,
+                          int64_t ignore_index) {
+  const long long n_rows = check_ce_shard(logits_shard, targets, vocab_start);
+  auto stats =
+      at::empty({n_rows, 3}, logits_shard.options().dtype(at::kFloat));
+  ce_shard_stats_launch(logits_shard.data_ptr(), targets.data_ptr(),
+                        stats.data_ptr(), n_rows, (int)logits_shard.size(-1),
+                        (int)vocab_start, (int)ignore_index, cur_stream());
+  return stats;
+}
+
+at::Tensor ce_shard_finish(at::Tensor& logits_shard, const at::Tensor& targets,
+                           int64_t vocab_start, const at::Tensor& stats_all,
+                           double grad_scale, int64_t ignore_index,
+                           bool compute_grad) {
+  const long long n_rows = check_ce_shard(logits_shard, targets, vocab_start);
+  TORCH_CHECK(stats_all.is_cuda() && stats_all.is_contiguous() &&
+                  stats_all.scalar_type() == at::kFloat,
+              "stats_all must be contiguous fp32 on GPU");
+  TORCH_CHECK(stats_all.dim() == 3 && stats_all.size(0) >= 1 &&
+                  stats_all.size(0) < (1LL << 31),
+              "stats_all must be [tp, N, 3]");
+  const long long tp = stats_all.size(0);
+  TORCH_CHECK(stats_all.numel() == tp * n_rows * 3,
+              "stats_all must hold tp*N*3 = ", tp * n_rows * 3,
+              " elements, got ", stats_all.numel());
+  auto losses = at::empty({n_rows}, logits_shard.options().dtype(at::kFloat));
+  ce_shard_finish_launch(logits_shard.data_ptr(), targets.data_ptr(),
+                         stats_all.data_ptr(), losses.data_ptr(), n_rows,
+                         (int)logits_shard.size(-1), (int)vocab_start, (int)tp,
+                         (int)ignore_index, (float)grad_scale,
+                         compute_grad ? 1 : 0, cur_stream());
+  return losses;
+}
+
 // ---- multi-tensor ops (multi_tensor.hip) ---------------------------------
 // span_elems == 0 picks the span from the list's total size; any other value
 // must be a multiple of 8 and is used as given.
@@ -635,6 +694,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "in-place softmax backward (bf16)");
   m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd,
         "fused CE loss + in-place dlogits (bf16)");
+  m.def("ce_shard_stats", &ce_shard_stats,
+        "vocab-parallel CE, stage 1: per-row (max, sumexp, target logit) of "
+        "one vocab shard -> fp32 [N,3]",
+        py::arg("logits_shard"), py::arg("targets"), py::arg("vocab_start"),
+        py::arg("ignore_index"));
+  m.def("ce_shard_finish", &ce_shard_finish,
+        "vocab-parallel CE, stage 2: combine stats_all [tp,N,3] -> losses, "
+        "in-place dlogits of the shard",
+        py::arg("logits_shard"), py::arg("targets"), py::arg("vocab_start"),
+        py::arg("stats_all"), py::arg("grad_scale"), py::arg("ignore_index"),
+        py::arg("compute_grad"));
   m.def("tr_b16_probe", []() {
     auto out = at::empty({64, 12}, at::TensorOptions()
                                       .dtype(at::kBFloat16)

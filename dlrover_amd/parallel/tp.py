@@ -101,6 +101,38 @@ class RowParallelLinear(nn.Module):
         return y
 
 
+class VocabParallelEmbedding(nn.Module):
+    """Embedding with the vocabulary rows split across TP: rank r holds ids
+    [r*V/tp, (r+1)*V/tp). Each rank looks up the ids it owns, contributes
+    zero rows for the rest, and the partial results are all-reduced. The
+    all-reduce's backward is the identity: every rank receives the full
+    output gradient and scatters only its own rows into its shard."""
+
+    def __init__(self, num_embeddings: int, dim: int, tp_size: int,
+                 tp_rank: int, tp_group=None):
+        super().__init__()
+        if num_embeddings % tp_size != 0:
+            raise ValueError(
+                f"num_embeddings {num_embeddings} % tp {tp_size} != 0"
+            )
+        self.tp_size = tp_size
+        self.tp_group = tp_group
+        self.per_rank = num_embeddings // tp_size
+        self.vocab_start = tp_rank * self.per_rank
+        self.weight = nn.Parameter(torch.empty(self.per_rank, dim))
+
+    def forward(self, ids):
+        if self.tp_size == 1:
+            return torch.nn.functional.embedding(ids, self.weight)
+        local = ids - self.vocab_start
+        foreign = (local < 0) | (local >= self.per_rank)
+        out = torch.nn.functional.embedding(
+            local.masked_fill(foreign, 0), self.weight
+        )
+        out = out.masked_fill(foreign.unsqueeze(-1), 0.0)
+        return reduce_from_tp(out, self.tp_group)
+
+
 def shard_full_weight(full: torch.Tensor, tp_rank: int, tp_size: int, dim: int
                       ) -> torch.Tensor:
     """Slice a replicated weight into this rank's TP shard."""

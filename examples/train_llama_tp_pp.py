@@ -10,6 +10,10 @@ engine on 8xMI355X").
 CPU plumbing (4 gloo ranks, tiny model):
     torchrun --standalone --nproc-per-node 4 examples/train_llama_tp_pp.py \
         --model tiny --tp 2 --pp 2 --steps 4 --seq 16
+
+--vocab-parallel shards embed, lm_head and the cross-entropy over the
+vocabulary across the TP group (they are replicated per TP rank otherwise);
+checkpoints of the two layouts are not interchangeable.
 """
 
 import argparse
@@ -42,6 +46,10 @@ def main():
     p.add_argument("--ckpt-dir", default="/tmp/dlrover_amd_ckpt/llama_tp_pp")
     p.add_argument("--progress-file", default="")
     p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--vocab-parallel", action="store_true",
+                   help="shard embed / lm_head / cross-entropy over the "
+                        "vocabulary across the TP group instead of "
+                        "replicating them on every TP rank")
     args = p.parse_args()
 
     use_gpu = torch.cuda.is_available()
@@ -82,7 +90,7 @@ def main():
         f"cuda:{local_rank % torch.cuda.device_count()}" if use_gpu else "cpu"
     )
     with device:
-        stage = LlamaStage(cfg, groups)
+        stage = LlamaStage(cfg, groups, vocab_parallel=args.vocab_parallel)
     stage = stage.to(device)
     if use_gpu:
         stage = stage.bfloat16()

@@ -26,6 +26,7 @@ sources = [
     os.path.join(CSRC, "multi_tensor.hip"),
     os.path.join(CSRC, "softmax.hip"),
     os.path.join(CSRC, "cross_entropy.hip"),
+    os.path.join(CSRC, "vocab_parallel_ce.hip"),
     os.path.join(CSRC, "mfma_probe.hip"),
     os.path.join(CSRC, "attention.hip"),
     os.path.join(CSRC, "attention_v3.hip"),
