@@ -16,6 +16,7 @@ on.
 """
 
 import os
+import pickle
 import queue as pyqueue
 import signal
 import threading
@@ -35,6 +36,7 @@ from dlrover_amd.common.storage import (
 from dlrover_amd.trainer.flash_checkpoint.shm_handler import (
     SharedMemoryHandler,
     shm_segment_name,
+    sums_file_name,
 )
 
 
@@ -70,7 +72,9 @@ def persist_shm_to_storage(
     else:
         path = event.path or os.path.join(checkpoint_dir, str(step))
     global_rank = meta.extra.get("global_rank", event.global_rank)
-    state = handler.load_state_dict()
+    # never verified here: the agent has no device, and the host reference
+    # is far too slow for a full state
+    state = handler.load_state_dict(verify=False)
     storage.safe_makedirs(path)
     shard_name = meta.extra.get("shard_name") or f"rank_{global_rank:05d}.pt"
     shard_file = os.path.join(path, shard_name)
@@ -78,6 +82,19 @@ def persist_shm_to_storage(
     t0 = time.perf_counter()
     torch.save(state, tmp)
     os.replace(tmp, shard_file)
+    sums = {
+        tm.path: tuple(tm.checksum)
+        for tm in meta.tensors
+        if getattr(tm, "checksum", None) is not None
+    }
+    if sums:
+        # sidecar with the checksums recorded at snapshot time, so a later
+        # load_from_storage can verify the shard; written before the done
+        # file so that a committed checkpoint always has it
+        sums_file = sums_file_name(shard_file)
+        with open(sums_file + ".tmp", "wb") as f:
+            pickle.dump(sums, f, protocol=pickle.HIGHEST_PROTOCOL)
+        os.replace(sums_file + ".tmp", sums_file)
     storage.write(str(step), _done_file(path, global_rank))
     logger.info(
         "persisted shard rank=%s step=%s (%.1f s) -> %s",

@@ -725,3 +725,193 @@ def fused_adamw_multi_step(
             steps[i],
             scale,
         )
+
+
+# ---------------------------------------------------------------------------
+# checkpoint integrity: per-tensor checksums, fused pack / unpack
+# ---------------------------------------------------------------------------
+
+_U64 = (1 << 64) - 1
+
+
+def _as_byte_array(buf):
+    """1-D uint8 numpy view of a CPU tensor, numpy array or bytes-like."""
+    import numpy as np
+
+    if isinstance(buf, torch.Tensor):
+        t = buf.detach()
+        if t.is_cuda:
+            t = t.cpu()
+        return t.contiguous().reshape(-1).view(torch.uint8).numpy()
+    if isinstance(buf, np.ndarray):
+        return np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
+    return np.frombuffer(buf, dtype=np.uint8)
+
+
+def ckpt_checksum_ref(buf, chunk_words: int = 1 << 20) -> Tuple[int, int]:
+    """Checksum ``(A, B)`` of a buffer's bytes (CPU tensor, numpy array or
+    bytes-like), as two Python ints below 2**64.
+
+    The bytes are extended with zero bytes to a multiple of 4 and read as
+    little-endian u32 words ``w_0 .. w_{W-1}``; ``A = sum w_i`` and
+    ``B = sum (2i+1) * w_i``, both mod 2**64. A single flipped bit always
+    changes ``A``; a swap of two different words always changes ``B`` (the
+    weights are odd and distinct); zero words contribute nothing, so padding
+    never matters; and any partition of the words gives the same bits, which
+    is what lets the device kernel (``ckpt_checksum``) spread them over blocks
+    and launches. This is an error-detection code against torn, stale or
+    damaged payloads, NOT a cryptographic hash: it offers no protection
+    against deliberate tampering.
+
+    numpy, in chunks of ``chunk_words`` so temporaries stay bounded. It serves
+    CPU tensors, the CPU tests and as the oracle of the device kernel; it is
+    not a path for large payloads: measured at about 0.2 GB/s on one host
+    core (256 MiB buffer), which is minutes for a 100 GB state."""
+    import numpy as np
+
+    raw = _as_byte_array(buf)
+    n = raw.size
+    full = n // 4
+    words = raw[: 4 * full].view("<u4")
+    a = 0
+    b = 0
+    chunk_words = max(int(chunk_words), 1)
+    with np.errstate(over="ignore"):
+        for c0 in range(0, full, chunk_words):
+            w = words[c0 : c0 + chunk_words].astype(np.uint64)
+            idx = np.arange(c0, c0 + w.size, dtype=np.uint64)
+            a += int(w.sum(dtype=np.uint64))
+            b += int(((idx * np.uint64(2) + np.uint64(1)) * w).sum(dtype=np.uint64))
+    if n > 4 * full:
+        last = int.from_bytes(raw[4 * full :].tobytes(), "little")
+        a += last
+        b += (2 * full + 1) * last
+    return a & _U64, b & _U64
+
+
+def ckpt_sums_to_ints(sums: torch.Tensor):
+    """``[N, 2]`` int64 sums (device or host) -> list of ``(A, B)`` Python
+    ints below 2**64. Reads the tensor on the host (synchronises a GPU)."""
+    return [(int(a) & _U64, int(b) & _U64) for a, b in sums.reshape(-1, 2).tolist()]
+
+
+def _ckpt_nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def ckpt_sum_slots(nbytes_list, span_bytes: int = 0) -> int:
+    """How many ``[slot, 2]`` int64 partial slots the device pack / unpack /
+    checksum needs for tensors of these byte sizes at this span (0 =
+    automatic). The CPU fallbacks need none."""
+    return int(hip_ops().ckpt_sum_slots([int(n) for n in nbytes_list], span_bytes))
+
+
+def _ckpt_workspace(tensors, dev, sums, partials, span_bytes):
+    n = len(tensors)
+    if sums is None:
+        sums = torch.empty((n, 2), device=dev, dtype=torch.int64)
+    if partials is None:
+        slots = ckpt_sum_slots([_ckpt_nbytes(t) for t in tensors], span_bytes)
+        partials = torch.empty((max(slots, 1), 2), device=dev, dtype=torch.int64)
+    return sums, partials
+
+
+def _ckpt_sums_cpu(tensors, sums):
+    """CPU fallback: the reference checksum of every tensor into sums."""
+    import numpy as np
+
+    vals = np.zeros((len(tensors), 2), dtype=np.uint64)
+    for i, t in enumerate(tensors):
+        vals[i] = ckpt_checksum_ref(t)
+    out = torch.from_numpy(vals.view(np.int64))
+    if sums is None:
+        return out
+    sums.reshape(-1)[: out.numel()].copy_(out.reshape(-1))
+    return sums
+
+
+def _ckpt_bytes(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().reshape(-1).view(torch.uint8)
+
+
+def ckpt_pack(
+    tensors,
+    offsets,
+    staging: torch.Tensor,
+    sums: Optional[torch.Tensor] = None,
+    partials: Optional[torch.Tensor] = None,
+    span_bytes: int = 0,
+) -> torch.Tensor:
+    """Copy the bytes of ``tensors[i]`` to ``staging[offsets[i]:...]`` (a flat
+    uint8 buffer) and return the checksums ``sums[N, 2]`` (int64, see
+    ``ckpt_checksum_ref``; row i belongs to tensor i). The ranges must not
+    overlap. Non-contiguous tensors are made contiguous first.
+
+    GPU: a few batched launches of one copy-with-checksum kernel plus a
+    finalize, no atomics, no allocation when ``sums`` and ``partials``
+    (``ckpt_sum_slots`` slots) are passed, no host sync: graph-capturable.
+    ``span_bytes`` (0 = automatic) is the bytes one block handles."""
+    tensors = [t.detach() for t in tensors]
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != len(tensors):
+        raise ValueError("ckpt_pack: one offset per tensor")
+    if _use_hip(staging, *tensors):
+        tensors = [t if t.numel() == 0 else t.contiguous() for t in tensors]
+        sums, partials = _ckpt_workspace(
+            tensors, staging.device, sums, partials, span_bytes
+        )
+        hip_ops().ckpt_copy_sum(0, tensors, staging, offsets, partials, sums, span_bytes)
+        return sums
+    for t, off in zip(tensors, offsets):
+        staging[off : off + _ckpt_nbytes(t)].copy_(_ckpt_bytes(t.contiguous()))
+    return _ckpt_sums_cpu(tensors, sums)
+
+
+def ckpt_unpack(
+    staging: torch.Tensor,
+    offsets,
+    tensors,
+    sums: Optional[torch.Tensor] = None,
+    partials: Optional[torch.Tensor] = None,
+    span_bytes: int = 0,
+) -> torch.Tensor:
+    """Inverse of ``ckpt_pack``: copy ``staging[offsets[i]:...]`` into the
+    (contiguous) ``tensors[i]`` and return the checksums of the bytes moved,
+    to be compared with the ones recorded at pack time."""
+    tensors = [t.detach() for t in tensors]
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != len(tensors):
+        raise ValueError("ckpt_unpack: one offset per tensor")
+    for t in tensors:
+        if t.numel() and not t.is_contiguous():
+            raise ValueError("ckpt_unpack: destination tensors must be contiguous")
+    if _use_hip(staging, *tensors):
+        sums, partials = _ckpt_workspace(
+            tensors, staging.device, sums, partials, span_bytes
+        )
+        hip_ops().ckpt_copy_sum(1, tensors, staging, offsets, partials, sums, span_bytes)
+        return sums
+    for t, off in zip(tensors, offsets):
+        _ckpt_bytes(t).copy_(staging[off : off + _ckpt_nbytes(t)])
+    return _ckpt_sums_cpu(tensors, sums)
+
+
+def ckpt_checksum(
+    tensors,
+    sums: Optional[torch.Tensor] = None,
+    partials: Optional[torch.Tensor] = None,
+    span_bytes: int = 0,
+) -> torch.Tensor:
+    """Checksums ``sums[N, 2]`` (int64) of a tensor list without copying
+    anything: the verify pass of a restore. GPU tensors are read once by the
+    pack kernel with no destination; CPU tensors go through
+    ``ckpt_checksum_ref``. ``ckpt_sums_to_ints`` turns the result into
+    Python ints."""
+    tensors = [t.detach() for t in tensors]
+    if _use_hip(*tensors):
+        tensors = [t if t.numel() == 0 else t.contiguous() for t in tensors]
+        dev = next(t.device for t in tensors if t.is_cuda)
+        sums, partials = _ckpt_workspace(tensors, dev, sums, partials, span_bytes)
+        hip_ops().ckpt_copy_sum(2, tensors, None, [], partials, sums, span_bytes)
+        return sums
+    return _ckpt_sums_cpu(tensors, sums)

@@ -73,6 +73,13 @@ void mt_adamw_launch(int, void* const*, const void* const*, void* const*,
                      const float*, const float*, const int*, int, float,
                      float, float, float, const float*, float, int, long long,
                      void*);
+int ckpt_span_quantum();
+int ckpt_max_blocks();
+long long ckpt_auto_span(long long);
+long long ckpt_num_slots(int, const long long*, long long);
+void ckpt_copy_sum_launch(int, const void* const*, void* const*,
+                          const long long*, long long, long long*, long long*,
+                          void*);
 }
 
 namespace {
@@ -674,6 +681,94 @@ void multi_tensor_adamw(
                   skip_nonfinite ? 1 : 0, span, cur_stream());
 }
 
+// ---- checkpoint pack / unpack / checksum (ckpt_pack.hip) ------------------
+// span_bytes == 0 picks the span from the list's total size; any other value
+// must be a multiple of the block's trip (threads x 16 bytes).
+long long ckpt_span(const std::vector<long long>& nbytes, int64_t span_bytes) {
+  const long long q = ckpt_span_quantum();
+  TORCH_CHECK(span_bytes >= 0 && span_bytes % q == 0 &&
+                  span_bytes < (1LL << 31),
+              "span_bytes must be 0 (automatic) or a positive multiple of ", q,
+              " below 2^31");
+  if (span_bytes > 0) return span_bytes;
+  long long total = 0;
+  for (long long n : nbytes) total += n;
+  return ckpt_auto_span(total);
+}
+
+int64_t ckpt_sum_slots(const std::vector<int64_t>& nbytes_list,
+                       int64_t span_bytes) {
+  std::vector<long long> nbytes(nbytes_list.begin(), nbytes_list.end());
+  for (long long n : nbytes) TORCH_CHECK(n >= 0, "negative nbytes");
+  return ckpt_num_slots((int)nbytes.size(), nbytes.data(),
+                        ckpt_span(nbytes, span_bytes));
+}
+
+// mode 0 (pack):   tensors[i] -> staging[offsets[i] ...)
+// mode 1 (unpack): staging[offsets[i] ...) -> tensors[i]
+// mode 2 (sum):    read tensors[i] only; staging and offsets unused
+// Every mode writes the checksum of tensor i's bytes to sums[i].
+void ckpt_copy_sum(int64_t mode, const std::vector<at::Tensor>& tensors,
+                   c10::optional<at::Tensor> staging,
+                   const std::vector<int64_t>& offsets, at::Tensor& partials,
+                   at::Tensor& sums, int64_t span_bytes) {
+  TORCH_CHECK(mode >= 0 && mode <= 2, "ckpt_copy_sum: mode must be 0, 1 or 2");
+  const int n = (int)tensors.size();
+  if (n == 0) return;
+  unsigned char* stage = nullptr;
+  long long stage_bytes = 0;
+  if (mode != 2) {
+    TORCH_CHECK(staging.has_value() && staging->is_cuda() &&
+                    staging->is_contiguous() &&
+                    staging->scalar_type() == at::kByte,
+                "ckpt: staging must be a contiguous uint8 tensor on GPU");
+    TORCH_CHECK((int)offsets.size() == n, "ckpt: one offset per tensor");
+    stage = (unsigned char*)staging->data_ptr();
+    stage_bytes = (long long)staging->numel();
+  }
+  std::vector<long long> nbytes(n);
+  std::vector<const void*> src(n);
+  std::vector<void*> dst(n, nullptr);
+  for (int i = 0; i < n; ++i) {
+    const auto& t = tensors[i];
+    TORCH_CHECK(t.is_cuda(), "ckpt: tensors must be on GPU");
+    TORCH_CHECK(t.numel() == 0 || t.is_contiguous(),
+                "ckpt: tensors must be contiguous");
+    nbytes[i] = (long long)t.numel() * (long long)t.element_size();
+    void* tp = nbytes[i] ? t.data_ptr() : nullptr;
+    void* sp = nullptr;
+    if (mode != 2) {
+      TORCH_CHECK(offsets[i] >= 0 && offsets[i] + nbytes[i] <= stage_bytes,
+                  "ckpt: tensor ", i, " at offset ", offsets[i], " with ",
+                  nbytes[i], " bytes does not fit the staging buffer of ",
+                  stage_bytes, " bytes");
+      sp = stage + offsets[i];
+    }
+    if (mode == 1) {
+      src[i] = sp;
+      dst[i] = tp;
+    } else {
+      src[i] = tp;
+      dst[i] = sp;
+    }
+  }
+  const long long span = ckpt_span(nbytes, span_bytes);
+  const long long need = ckpt_num_slots(n, nbytes.data(), span);
+  TORCH_CHECK(need < (1LL << 31), "ckpt: too many spans");
+  TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
+                  partials.scalar_type() == at::kLong &&
+                  partials.numel() >= 2 * need,
+              "ckpt: partials must be contiguous int64 on GPU with at least ",
+              need, " x 2 elements");
+  TORCH_CHECK(sums.is_cuda() && sums.is_contiguous() &&
+                  sums.scalar_type() == at::kLong && sums.numel() >= 2LL * n,
+              "ckpt: sums must be contiguous int64 on GPU with at least ", n,
+              " x 2 elements");
+  ckpt_copy_sum_launch(n, src.data(), mode == 2 ? nullptr : dst.data(),
+                       nbytes.data(), span, (long long*)partials.data_ptr(),
+                       (long long*)sums.data_ptr(), cur_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -745,4 +840,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("beta2"), py::arg("eps"), py::arg("grad_scale"),
         py::arg("norm_sq"), py::arg("max_norm"), py::arg("skip_nonfinite"),
         py::arg("span_elems") = 0);
+  m.attr("CKPT_SPAN_QUANTUM") = ckpt_span_quantum();
+  m.attr("CKPT_MAX_BLOCKS") = ckpt_max_blocks();
+  m.def("ckpt_auto_span", [](int64_t total) {
+    return (int64_t)ckpt_auto_span((long long)total);
+  }, "span in bytes that ckpt_copy_sum picks for a list of this total size");
+  m.def("ckpt_sum_slots", &ckpt_sum_slots,
+        "[slots, 2] int64 partial slots ckpt_copy_sum needs for these sizes",
+        py::arg("nbytes_list"), py::arg("span_bytes") = 0);
+  m.def("ckpt_copy_sum", &ckpt_copy_sum,
+        "batched copy (0 pack, 1 unpack, 2 none) with per-tensor checksums "
+        "-> sums[N,2] (int64, no atomics)",
+        py::arg("mode"), py::arg("tensors"), py::arg("staging"),
+        py::arg("offsets"), py::arg("partials"), py::arg("sums"),
+        py::arg("span_bytes") = 0);
 }

@@ -17,8 +17,7 @@
 // fixed order (fp64), so the norm — and with it every clipped update — is
 // bitwise reproducible from run to run.
 #include "kern_common.h"
-
-#include <string.h>
+#include "mt_launch.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
@@ -50,13 +49,11 @@ struct MTBatch {
   int pad_;
 };
 
-static_assert(MT_MAX_TENSORS <= 256, "block->tensor map is u8");
 // kernel-argument limit; leave room for the other (and hidden) arguments
 static_assert(sizeof(MTBatch) <= 4096 - 512, "MTBatch must fit kernel args");
 
 __device__ __forceinline__ int mt_block_tensor(const MTBatch& b) {
-  const unsigned blk = blockIdx.x;
-  return (int)((b.block_tensor[blk >> 2] >> ((blk & 3u) * 8u)) & 0xffu);
+  return mt_block_entry(b.block_tensor);
 }
 
 // ---------------------------------------------------------------------------
@@ -256,51 +253,19 @@ inline bool misaligned16(const void* p) {
   return p != nullptr && ((uintptr_t)p & 15u) != 0;
 }
 
-inline long long spans_of(long long numel, long long span) {
-  return (numel + span - 1) / span;
-}
-
-// fill(i, entry) sets everything but span_bias; launch(batch, n_blocks) fires
-// one kernel. Zero-numel tensors are skipped.
+// fill(i, entry) sets everything but numel and span_bias; launch(batch,
+// n_blocks) fires one kernel. Zero-numel tensors are skipped. The cutting
+// itself is mt_cut_launches (mt_launch.h), shared with ckpt_pack.hip.
 template <class Fill, class Launch>
 void mt_for_each_launch(int n, const long long* numel, long long span,
                         Fill fill, Launch launch) {
-  MTBatch batch;
-  memset(&batch, 0, sizeof(batch));
-  batch.span = span;
-  int nt = 0, nb = 0;
-  long long global_block = 0;
-  auto flush = [&]() {
-    if (nb == 0) return;
-    batch.partial_base = (int)global_block;
-    launch(batch, nb);
-    global_block += nb;
-    memset(&batch, 0, sizeof(batch));
-    batch.span = span;
-    nt = nb = 0;
-  };
-  for (int i = 0; i < n; ++i) {
-    if (numel[i] <= 0) continue;
-    const long long spans = spans_of(numel[i], span);
-    long long s = 0;
-    while (s < spans) {
-      if (nt == MT_MAX_TENSORS || nb == MT_MAX_BLOCKS) flush();
-      long long take = spans - s;
-      if (take > MT_MAX_BLOCKS - nb) take = MT_MAX_BLOCKS - nb;
-      MTTensor& e = batch.t[nt];
-      fill(i, e);
-      e.numel = numel[i];
-      e.span_bias = (int)(s - nb);
-      for (long long k = 0; k < take; ++k) {
-        const unsigned blk = (unsigned)(nb + k);
-        batch.block_tensor[blk >> 2] |= (unsigned)nt << ((blk & 3u) * 8u);
-      }
-      nb += (int)take;
-      nt += 1;
-      s += take;
-    }
-  }
-  flush();
+  mt_cut_launches<MTBatch, MT_MAX_TENSORS, MT_MAX_BLOCKS>(
+      n, numel, span,
+      [&](int i, MTTensor& e) {
+        fill(i, e);
+        e.numel = numel[i];
+      },
+      launch);
 }
 
 }  // namespace
@@ -328,7 +293,7 @@ extern "C" long long mt_num_blocks(int n, const long long* numel,
                                    long long span) {
   long long total = 0;
   for (int i = 0; i < n; ++i)
-    if (numel[i] > 0) total += spans_of(numel[i], span);
+    if (numel[i] > 0) total += mt_spans_of(numel[i], span);
   return total;
 }
 

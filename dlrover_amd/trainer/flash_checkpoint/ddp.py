@@ -19,11 +19,16 @@ from dlrover_amd.trainer.flash_checkpoint.engine import FullCheckpointEngine
 
 
 class DdpCheckpointer(Checkpointer):
-    def __init__(self, checkpoint_dir: str, model=None, optimizer=None, storage=None):
+    def __init__(self, checkpoint_dir: str, model=None, optimizer=None,
+                 storage=None, checksum: Optional[bool] = None):
+        # checksum: per-tensor checkpoint checksums, verified on every load;
+        # None reads DLROVER_CKPT_CHECKSUM (default off)
         self.checkpoint_dir = checkpoint_dir
         self.model = model
         self.optimizer = optimizer
-        self.engine = FullCheckpointEngine(checkpoint_dir, storage=storage)
+        self.engine = FullCheckpointEngine(
+            checkpoint_dir, storage=storage, checksum=checksum
+        )
 
     def _state_dict(self, step: int):
         mod = self.model.module if hasattr(self.model, "module") else self.model

@@ -50,7 +50,8 @@ class DeepSpeedCheckpointEngine(CheckpointEngine):
 
 
 class DeepSpeedCheckpointer(Checkpointer):
-    def __init__(self, model_engine, checkpoint_dir: str, storage=None):
+    def __init__(self, model_engine, checkpoint_dir: str, storage=None,
+                 checksum: Optional[bool] = None):
         try:
             import deepspeed  # noqa: F401
         except ImportError as e:
@@ -61,7 +62,9 @@ class DeepSpeedCheckpointer(Checkpointer):
             ) from e
         self.model_engine = model_engine
         self.checkpoint_dir = checkpoint_dir
-        self.engine = DeepSpeedCheckpointEngine(checkpoint_dir, storage=storage)
+        self.engine = DeepSpeedCheckpointEngine(
+            checkpoint_dir, storage=storage, checksum=checksum
+        )
 
     def save_checkpoint(self, step: int, state_dict: Optional[dict] = None,
                         path: str = "", storage_type: int = StorageType.DISK

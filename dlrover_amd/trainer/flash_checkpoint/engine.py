@@ -34,8 +34,12 @@ from dlrover_amd.common.storage import (
     read_tracker_step,
 )
 from dlrover_amd.trainer.flash_checkpoint.shm_handler import (
+    CheckpointCorruptError,
     SharedMemoryHandler,
+    DEVICE_COPY_HEADROOM,
     shm_segment_name,
+    sums_file_name,
+    traverse_state_dict,
 )
 
 CKPT_EVENT_QUEUE = "flash_ckpt_events"
@@ -54,6 +58,12 @@ class CheckpointEvent:
     global_rank: int = 0
     world_size: int = 1
     expected_shards: int = 1
+
+
+def checksum_from_env() -> bool:
+    """DLROVER_CKPT_CHECKSUM=1 turns checkpoint checksums on for every engine
+    that was not told otherwise (default: off)."""
+    return os.getenv("DLROVER_CKPT_CHECKSUM", "0").lower() in ("1", "true", "on")
 
 
 def _local_rank() -> int:
@@ -86,6 +96,11 @@ class CheckpointEngine:
     save_to_memory(step, state_dict)  -> blocking seconds (training stall)
     save_to_storage(step, state_dict, path) -> same + async persist event
     load(path=None) -> state_dict from shm (hit) or storage
+
+    checksum: record a per-tensor checksum with every snapshot and verify it
+    on every load (shm, replica, storage). None reads the environment
+    variable DLROVER_CKPT_CHECKSUM; the default is off, and off changes
+    nothing about the paths, files and formats.
     """
 
     def __init__(
@@ -94,14 +109,17 @@ class CheckpointEngine:
         storage=None,
         comm_backend: str = "",
         save_timeout: int = CheckpointConstant.SAVE_TIMEOUT,
+        checksum: Optional[bool] = None,
     ):
         self.checkpoint_dir = checkpoint_dir
         self.storage = storage or PosixDiskStorage()
         self._save_timeout = save_timeout
         self._local_rank = _local_rank()
         self._job = os.getenv("ELASTIC_JOB_NAME", "default")
+        self._checksum = checksum_from_env() if checksum is None else bool(checksum)
         self.shm_handler = SharedMemoryHandler(
-            shm_segment_name(self._job, self._local_rank)
+            shm_segment_name(self._job, self._local_rank),
+            checksum=self._checksum,
         )
         self._agent_mode = os.path.exists(ipc_socket_path())
         if self._agent_mode:
@@ -219,9 +237,24 @@ class CheckpointEngine:
 
     # -- load ------------------------------------------------------------------
 
+    def _load_from_shm(self, handler: SharedMemoryHandler, **kw) -> Optional[Any]:
+        """handler.load_state_dict, except that a snapshot that fails its
+        checksums counts as a miss: the error is logged with the offending
+        tensors and the caller falls through to its next source. Nothing but
+        CheckpointCorruptError is caught."""
+        try:
+            return handler.load_state_dict(**kw)
+        except CheckpointCorruptError as e:
+            logger.error(
+                "shm snapshot %s is corrupt, falling back to storage: %s",
+                handler.name, e,
+            )
+            return None
+
     def load(self, path: str = "", device: Optional[torch.device] = None) -> Optional[Any]:
-        """shm hit first (ref: engine.py load :534), else storage."""
-        sd = self.shm_handler.load_state_dict(device=device)
+        """shm hit first (ref: engine.py load :534), else storage. A shm
+        snapshot that fails its checksums is skipped like a miss."""
+        sd = self._load_from_shm(self.shm_handler, device=device)
         if sd is not None:
             return sd
         return self.load_from_storage(path, device=device)
@@ -237,7 +270,50 @@ class CheckpointEngine:
         shard = os.path.join(path, self._shard_file_name(_global_rank()))
         if not os.path.exists(shard):
             return None
-        return torch.load(shard, map_location=device or "cpu", weights_only=False)
+        sd = torch.load(shard, map_location=device or "cpu", weights_only=False)
+        self._verify_loaded_shard(sd, shard)
+        return sd
+
+    def _verify_loaded_shard(self, state_dict: Any, shard_file: str):
+        """Check a state dict loaded from `shard_file` against its checksum
+        sidecar. No sidecar (old checkpoints, checksums off at save time) or
+        checksums disabled on this engine: no verification. GPU tensors are
+        summed by one batched kernel call, CPU tensors by the host reference.
+        Raises CheckpointCorruptError(source="storage")."""
+        if not self._checksum:
+            return
+        sidecar = sums_file_name(shard_file)
+        if not os.path.exists(sidecar):
+            return
+        import pickle
+
+        with open(sidecar, "rb") as f:
+            recorded = pickle.load(f)
+        from dlrover_amd.ops.api import (
+            ckpt_checksum,
+            ckpt_checksum_ref,
+            ckpt_sums_to_ints,
+        )
+
+        leaves = {
+            tuple(p): v
+            for p, v in traverse_state_dict(state_dict)
+            if isinstance(v, torch.Tensor)
+        }
+        bad = [p for p in recorded if tuple(p) not in leaves]
+        on_gpu = [(p, leaves[tuple(p)]) for p in recorded
+                  if tuple(p) in leaves and leaves[tuple(p)].is_cuda]
+        on_cpu = [(p, leaves[tuple(p)]) for p in recorded
+                  if tuple(p) in leaves and not leaves[tuple(p)].is_cuda]
+        for p, t in on_cpu:
+            if ckpt_checksum_ref(t) != tuple(recorded[p]):
+                bad.append(p)
+        if on_gpu:
+            got = ckpt_sums_to_ints(ckpt_checksum([t for _, t in on_gpu]))
+            bad += [p for (p, _), have in zip(on_gpu, got)
+                    if have != tuple(recorded[p])]
+        if bad:
+            raise CheckpointCorruptError(bad, source="storage")
 
     @staticmethod
     def _shard_file_name(global_rank: int) -> str:
@@ -336,13 +412,14 @@ class FullCheckpointEngine(CheckpointEngine):
         """Full-checkpoint load order: own shm, local rank 0's shm (the full
         state lives there on this node), then storage. All ranks MUST resolve
         the same step or DDP ranks would resume divergent and deadlock."""
-        sd = self.shm_handler.load_state_dict(device=device)
+        sd = self._load_from_shm(self.shm_handler, device=device)
         if sd is None and self._local_rank != 0:
             h0 = SharedMemoryHandler(
-                shm_segment_name(self._job, 0), host_pin=False
+                shm_segment_name(self._job, 0), host_pin=False,
+                checksum=self._checksum,
             )
             if h0.attach():
-                sd = h0.load_state_dict(device=device)
+                sd = self._load_from_shm(h0, device=device)
                 h0.close()
         if sd is None:
             sd = self.load_from_storage(path, device=device)
@@ -472,11 +549,48 @@ class ShardedCheckpointEngine(CheckpointEngine):
                 dst = _to_local(name2p[name].data)
                 dst.copy_(st["master_param"].to(dst.dtype))
 
+    def _verified_device_restore_fits(self) -> bool:
+        """Should restore_into take the device-verified path, and can it?"""
+        if not (self._checksum and torch.cuda.is_available()):
+            return False
+        meta = self.shm_handler.read_meta()
+        if meta is None or not any(
+            getattr(tm, "checksum", None) is not None for tm in meta.tensors
+        ):
+            return False
+        free, _total = torch.cuda.mem_get_info()
+        if meta.payload_bytes + DEVICE_COPY_HEADROOM < free:
+            return True
+        logger.warning(
+            "verified restore needs a transient %.1f GB device copy but only "
+            "%.1f GB are free: restoring UNVERIFIED from shm",
+            meta.payload_bytes / (1 << 30), free / (1 << 30),
+        )
+        return False
+
     def restore_into(self, model, optimizer, path: str = ""):
         """Fast-path restore: zero-copy shm views -> async H2D into the live
         param/optimizer storage. Returns the loaded state dict skeleton or
-        None when neither shm nor storage has a checkpoint."""
-        sd = self.shm_handler.load_state_dict(zero_copy=True)
+        None when neither shm nor storage has a checkpoint.
+
+        With checksums enabled on a GPU the shm snapshot is instead loaded
+        to the device, verified there by the checksum kernel, and copied
+        device-to-device into the live storage. That holds a transient
+        SECOND copy of the state in HBM; when it would not fit (with the
+        stager's 24 GiB headroom) a warning is logged and the restore runs
+        unverified through the zero-copy path. A snapshot that fails its
+        checksums is skipped and the restore continues from storage."""
+        if self._verified_device_restore_fits():
+            sd = self._load_from_shm(
+                self.shm_handler, device=torch.device("cuda"), verify=True
+            )
+        else:
+            # on a GPU this is the unverified fast path; without one the
+            # handler's default applies (host verification when enabled)
+            verify = False if torch.cuda.is_available() else None
+            sd = self._load_from_shm(
+                self.shm_handler, zero_copy=True, verify=verify
+            )
         if sd is None:
             sd = self.load_from_storage(path)
         if sd is None:

@@ -21,11 +21,17 @@ from dlrover_amd.trainer.flash_checkpoint.engine import ShardedCheckpointEngine
 
 
 class FsdpShardCheckpointer(Checkpointer):
-    def __init__(self, checkpoint_dir: str, model=None, optimizer=None, storage=None):
+    def __init__(self, checkpoint_dir: str, model=None, optimizer=None,
+                 storage=None, checksum: Optional[bool] = None):
+        # checksum: per-tensor checkpoint checksums, computed inside the
+        # fused device snapshot and verified on every load; None reads
+        # DLROVER_CKPT_CHECKSUM (default off)
         self.checkpoint_dir = checkpoint_dir
         self.model = model
         self.optimizer = optimizer
-        self.engine = ShardedCheckpointEngine(checkpoint_dir, storage=storage)
+        self.engine = ShardedCheckpointEngine(
+            checkpoint_dir, storage=storage, checksum=checksum
+        )
 
     def save_checkpoint(
         self,

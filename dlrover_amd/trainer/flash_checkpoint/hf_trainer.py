@@ -24,14 +24,17 @@ class FlashCkptTrainer(Trainer):  # type: ignore[misc]
     args.output_dir/checkpoint-<step>/ through the flash engine; the newest
     committed step is discoverable via get_last_checkpoint()."""
 
-    def __init__(self, *args, flash_checkpoint_dir: str = "", **kwargs):
+    def __init__(self, *args, flash_checkpoint_dir: str = "",
+                 flash_checkpoint_checksum=None, **kwargs):
         if not _HAS_TRANSFORMERS:
             raise ImportError("transformers is not installed")
         super().__init__(*args, **kwargs)
         from dlrover_amd.trainer.flash_checkpoint.ddp import DdpCheckpointer
 
         ckpt_dir = flash_checkpoint_dir or self.args.output_dir
-        self._flash = DdpCheckpointer(ckpt_dir)
+        self._flash = DdpCheckpointer(
+            ckpt_dir, checksum=flash_checkpoint_checksum
+        )
 
     def _save_checkpoint(self, model, trial=None, metrics=None):
         step = int(self.state.global_step)

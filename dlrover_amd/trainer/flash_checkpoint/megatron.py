@@ -89,13 +89,18 @@ class TpPpCheckpointEngine(CheckpointEngine):
         if not use_bcast:
             if not os.path.exists(shard):
                 return None
-            return torch.load(shard, map_location=device or "cpu",
-                              weights_only=False)
+            sd = torch.load(shard, map_location=device or "cpu",
+                            weights_only=False)
+            self._verify_loaded_shard(sd, shard)
+            return sd
         obj = [None]
         if g.dp_rank == 0:
             if os.path.exists(shard):
                 obj[0] = torch.load(shard, map_location="cpu",
                                     weights_only=False)
+                # the one reader verifies (host reference) before it
+                # broadcasts; a corrupt shard raises on dp_rank 0
+                self._verify_loaded_shard(obj[0], shard)
         # global rank of this (tp, pp) pair's dp_rank-0 member
         src = g.pp_rank * g.dims.tp + g.tp_rank
         dist.broadcast_object_list(obj, src=src, group=g.dp_group)
@@ -106,11 +111,14 @@ class MegatronCheckpointer(Checkpointer):
     """User-facing TP/PP checkpointer (ref: flash_checkpoint/megatron.py:54)."""
 
     def __init__(self, checkpoint_dir: str, groups: ParallelGroups,
-                 model=None, optimizer=None, storage=None):
+                 model=None, optimizer=None, storage=None,
+                 checksum: Optional[bool] = None):
         self.checkpoint_dir = checkpoint_dir
         self.model = model
         self.optimizer = optimizer
-        self.engine = TpPpCheckpointEngine(checkpoint_dir, groups, storage=storage)
+        self.engine = TpPpCheckpointEngine(
+            checkpoint_dir, groups, storage=storage, checksum=checksum
+        )
 
     def save_checkpoint(
         self,

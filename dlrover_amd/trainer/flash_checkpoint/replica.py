@@ -86,6 +86,9 @@ class ReplicaManager:
         payload = len(raw) - self.handler._payload_offset()
         self.handler.ensure_size(max(payload, 1))
         self.handler._shm.buf[: len(raw)] = raw
+        # the meta (checksums included) rode along, so the handler's normal
+        # load verifies these bytes; a mismatch is reported as ours
+        self.handler.corrupt_source = "replica"
 
     def _backup_name(self) -> str:
         return f"{self.handler.name}_backup"

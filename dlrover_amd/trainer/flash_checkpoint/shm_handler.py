@@ -36,11 +36,29 @@ from dlrover_amd.common.multi_process import (
     create_shared_memory,
     unlink_shared_memory,
 )
+from dlrover_amd.ops.api import (
+    ckpt_checksum,
+    ckpt_checksum_ref,
+    ckpt_pack,
+    ckpt_sums_to_ints,
+)
 from dlrover_amd.utils import hipmem
 
 _ALIGN = 64
 _META_CAPACITY = 8 << 20  # 8 MiB reserved for pickled metadata
 _PAYLOAD_OFFSET_BASE = 16
+# free HBM to leave for transient allocations (restore/rescale paths) when a
+# full-size device copy of the checkpoint is about to be made
+DEVICE_COPY_HEADROOM = 24 << 30
+
+
+def sums_file_name(shard_file: str) -> str:
+    """Checksum sidecar of a shard file: rank_00003.pt -> rank_00003.sums. A
+    pickled {tensor path: (A, B)} written next to the shard when the
+    snapshot carries checksums; the .pt format itself is unchanged."""
+    import os
+
+    return os.path.splitext(shard_file)[0] + ".sums"
 
 
 def shm_segment_name(job_name: str, local_rank: int) -> str:
@@ -54,6 +72,30 @@ class TensorMeta:
     dtype: str  # torch dtype name, e.g. "bfloat16"
     offset: int  # byte offset into the payload region
     nbytes: int
+    # (A, B) of ops.api.ckpt_checksum_ref over the tensor's bytes; None when
+    # the snapshot was saved without checksums (and in metas pickled before
+    # the field existed, which fall back to this class default)
+    checksum: Optional[Tuple[int, int]] = None
+
+
+class CheckpointCorruptError(RuntimeError):
+    """Restored bytes are not the bytes that were saved: the checksum of at
+    least one tensor differs from the one recorded at save time.
+
+    ``paths`` are the key paths of the offending tensors, ``source`` names
+    where the bytes came from: "shm", "storage" or "replica"."""
+
+    def __init__(self, paths, source: str = "shm", step: int = -1):
+        self.paths = [tuple(p) for p in paths]
+        self.source = source
+        self.step = step
+        names = ", ".join("/".join(str(k) for k in p) for p in self.paths[:8])
+        if len(self.paths) > 8:
+            names += f", ... ({len(self.paths)} in all)"
+        super().__init__(
+            f"checkpoint from {source} (step {step}) failed its checksum in "
+            f"{len(self.paths)} tensor(s): {names}"
+        )
 
 
 @dataclass
@@ -148,8 +190,15 @@ def plan_layout(state_dict: Any) -> SegmentMeta:
 class SharedMemoryHandler:
     """Owns one shm segment for one local rank."""
 
-    def __init__(self, name: str, host_pin: bool = True):
+    def __init__(self, name: str, host_pin: bool = True, checksum: bool = False):
         self.name = name
+        # checksum=True: saves record a per-tensor checksum in the meta (GPU
+        # tensors: computed by the fused pack kernel during the device
+        # snapshot) and loads verify it by default
+        self._checksum = bool(checksum)
+        # what a CheckpointCorruptError from this segment reports as source;
+        # ReplicaManager sets "replica" when it fills the segment from a peer
+        self.corrupt_source = "shm"
         self._shm = None
         self._pinned = False
         self._host_pin = host_pin
@@ -282,9 +331,11 @@ class SharedMemoryHandler:
         meta.step = step
         meta.extra = extra or {}
         self.ensure_size(meta.payload_bytes)
+        self.corrupt_source = "shm"  # whatever a replica put here is gone
         with self._lock:
             self._write_commit(0)  # invalidate during write
         gpu_tensors = []
+        cpu_writes = []
         host_view = np.frombuffer(
             self._shm.buf, dtype=np.uint8, count=meta.payload_bytes,
             offset=self._payload_offset(),
@@ -296,17 +347,40 @@ class SharedMemoryHandler:
             else:
                 src = t.contiguous().view(-1).view(torch.uint8).numpy()
                 host_view[tm.offset : tm.offset + tm.nbytes] = src
+                if self._checksum:
+                    tm.checksum = ckpt_checksum_ref(src)
+                cpu_writes.append((tm, src))
         if gpu_tensors:
             if self._stager is None:
                 self._stager = _DeviceStager()
-            self._stager.snapshot(gpu_tensors)  # blocking: HBM->HBM, ms-class
-            done_evt = self._stager.drain_async(host_view, self._pinned)
+            # blocking: HBM->HBM, ms-class
+            self._stager.snapshot(gpu_tensors, checksum=self._checksum)
+            stager = self._stager
+            # the unchunked drain is ONE copy of staging[0:payload) and so
+            # runs over the regions of CPU tensors that lie in front of the
+            # last GPU tensor; keep the bytes of those (step counters and
+            # the like) and put them back once the drain is through. The
+            # chunked drain copies tensor by tensor and overwrites nothing.
+            if stager._chunked:
+                cpu_writes = []
+            else:
+                cpu_writes = [
+                    (tm, src.copy()) for tm, src in cpu_writes
+                    if tm.offset < stager._payload
+                ]
+            done_evt = stager.drain_async(host_view, self._pinned)
             # chunked staging drains synchronously (live sources) — the
             # honest blocking time then includes the PCIe drain
             blocking = time.perf_counter() - t0
 
             def _finish():
                 done_evt.synchronize()
+                for tm, src in cpu_writes:
+                    host_view[tm.offset : tm.offset + tm.nbytes] = src
+                if self._checksum:
+                    # the sums followed the payload on the drain stream
+                    for (tm, _), pair in zip(gpu_tensors, stager.host_sums()):
+                        tm.checksum = pair
                 with self._lock:
                     self._write_meta(meta)
                     self._write_commit(step)
@@ -330,9 +404,20 @@ class SharedMemoryHandler:
     # -- read path -------------------------------------------------------------
 
     def load_state_dict(
-        self, device: Optional[torch.device] = None, zero_copy: bool = False
+        self,
+        device: Optional[torch.device] = None,
+        zero_copy: bool = False,
+        verify: Optional[bool] = None,
     ) -> Optional[Any]:
         """Reconstruct the state dict from shm (returns None if empty).
+
+        verify: check every tensor that carries a checksum in the meta and
+        raise CheckpointCorruptError on a mismatch. None (default) verifies
+        iff the handler was built with checksum=True. A snapshot saved
+        without checksums loads unverified whatever the flag. With a GPU
+        device the NEW DEVICE tensors are summed by one batched kernel call
+        (so the H2D copy is covered too); without one the host reference
+        runs per tensor, which is slow for large payloads.
 
         zero_copy=True returns tensors that VIEW the shm mapping directly —
         no host-side copy at all. The caller must copy them into its own
@@ -348,8 +433,15 @@ class SharedMemoryHandler:
         )
         pairs = list(meta.objects)
         to_gpu = device is not None and device.type != "cpu"
-        for tm in meta.tensors:
-            view = torch.from_numpy(host[tm.offset : tm.offset + tm.nbytes])
+        if verify is None:
+            verify = self._checksum
+        expected = [getattr(tm, "checksum", None) for tm in meta.tensors]
+        verify = bool(verify) and any(c is not None for c in expected)
+        loaded = []
+        bad = []
+        for tm, want in zip(meta.tensors, expected):
+            raw = host[tm.offset : tm.offset + tm.nbytes]
+            view = torch.from_numpy(raw)
             view = view.view(getattr(torch, tm.dtype)).view(tm.shape)
             if to_gpu:
                 t = torch.empty_like(view, device=device)
@@ -358,9 +450,33 @@ class SharedMemoryHandler:
                 t = view
             else:
                 t = view.clone()
+            if verify and not to_gpu and want is not None:
+                if ckpt_checksum_ref(raw) != tuple(want):
+                    bad.append(tm.path)
+            loaded.append(t)
             pairs.append((tm.path, t))
         if to_gpu:
+            sums_host = None
+            if verify:
+                # one batched kernel call over the device tensors; its single
+                # host read rides on the synchronize below
+                sums = ckpt_checksum(loaded)
+                sums_host = torch.empty(
+                    sums.shape, dtype=sums.dtype, pin_memory=True
+                )
+                sums_host.copy_(sums, non_blocking=True)
             torch.cuda.synchronize()
+            if sums_host is not None:
+                got = ckpt_sums_to_ints(sums_host)
+                bad = [
+                    tm.path
+                    for tm, want, have in zip(meta.tensors, expected, got)
+                    if want is not None and tuple(want) != have
+                ]
+        if bad:
+            raise CheckpointCorruptError(
+                bad, source=self.corrupt_source, step=meta.step
+            )
         state = _build_skeleton(pairs)
         return state
 
@@ -397,6 +513,35 @@ class _DeviceStager:
         self._payload = 0
         self._chunked = False
         self._pending: List[Tuple[TensorMeta, torch.Tensor]] = []
+        # checksum workspaces, grown on demand and reused from save to save
+        self._sums: Optional[torch.Tensor] = None  # [N, 2] int64, device
+        self._partials: Optional[torch.Tensor] = None  # [slots, 2] int64
+        self._sums_host: Optional[torch.Tensor] = None  # pinned [N, 2]
+        self._n_sums = 0  # 0: the current snapshot carries no checksums
+
+    def _sum_workspace(self, nbytes_list):
+        """(sums, partials) for this tensor list; allocates only when the
+        list outgrew what the previous saves needed."""
+        from dlrover_amd.ops.api import ckpt_sum_slots
+
+        n = len(nbytes_list)
+        slots = max(ckpt_sum_slots(nbytes_list), 1)
+        if self._sums is None or self._sums.shape[0] < n:
+            self._sums = torch.empty((n, 2), dtype=torch.int64, device="cuda")
+            self._sums_host = torch.empty(
+                (n, 2), dtype=torch.int64, pin_memory=True
+            )
+        if self._partials is None or self._partials.shape[0] < slots:
+            self._partials = torch.empty(
+                (slots, 2), dtype=torch.int64, device="cuda"
+            )
+        self._n_sums = n
+        return self._sums[:n], self._partials
+
+    def host_sums(self) -> List[Tuple[int, int]]:
+        """Checksums of the last snapshot's tensors, in snapshot order. Valid
+        once the event returned by drain_async has completed."""
+        return ckpt_sums_to_ints(self._sums_host[: self._n_sums])
 
     def _ensure(self, payload: int):
         if self._buf is not None and self._buf.numel() >= payload and not self._chunked:
@@ -407,7 +552,7 @@ class _DeviceStager:
             free = 0  # test hook: exercise the chunked fallback on any size
         # generous headroom: restore/rescale paths need transient allocations;
         # a staging buffer that "just fits" starves them (8B @ N=1 OOM'd)
-        if payload + (24 << 30) < free:
+        if payload + DEVICE_COPY_HEADROOM < free:
             self._chunked = False
             self._buf = torch.empty(payload, dtype=torch.uint8, device="cuda")
         else:
@@ -417,18 +562,50 @@ class _DeviceStager:
                     min(2 * self.CHUNK, payload), dtype=torch.uint8, device="cuda"
                 )
 
-    def snapshot(self, tensors: List[Tuple[TensorMeta, torch.Tensor]]):
+    def snapshot(
+        self,
+        tensors: List[Tuple[TensorMeta, torch.Tensor]],
+        checksum: bool = False,
+    ):
+        """checksum=True replaces the per-tensor copy_ loop by the fused
+        multi-tensor pack kernel: the same HBM->HBM bytes in a handful of
+        launches, with every tensor's checksum produced from the registers
+        the copy already holds."""
         payload = max(tm.offset + tm.nbytes for tm, _ in tensors)
         self._ensure(payload)
         self._payload = payload
+        self._n_sums = 0
+        stream = torch.cuda.current_stream()
         if self._chunked:
             self._pending = tensors
+            if checksum:
+                # no full device snapshot exists: sum the live sources now,
+                # before the synchronous drain copies them out
+                srcs = [t.contiguous() for _, t in tensors]
+                sums, partials = self._sum_workspace([tm.nbytes for tm, _ in tensors])
+                ckpt_checksum(srcs, sums=sums, partials=partials)
+                stream.synchronize()
             return
-        stream = torch.cuda.current_stream()
-        for tm, t in tensors:
-            src = t.contiguous().view(-1).view(torch.uint8)
-            self._buf[tm.offset : tm.offset + tm.nbytes].copy_(src)
+        if checksum:
+            srcs = [t.contiguous() for _, t in tensors]
+            sums, partials = self._sum_workspace([tm.nbytes for tm, _ in tensors])
+            ckpt_pack(
+                srcs, [tm.offset for tm, _ in tensors], self._buf,
+                sums=sums, partials=partials,
+            )
+        else:
+            for tm, t in tensors:
+                src = t.contiguous().view(-1).view(torch.uint8)
+                self._buf[tm.offset : tm.offset + tm.nbytes].copy_(src)
         stream.synchronize()  # snapshot complete: optimizer may mutate params
+
+    def _drain_sums(self):
+        """D2H of the [N, 2] sums on the drain stream, after the payload. The
+        kernels that wrote them finished before snapshot() returned."""
+        if self._n_sums:
+            self._sums_host[: self._n_sums].copy_(
+                self._sums[: self._n_sums], non_blocking=True
+            )
 
     def drain_async(self, host_view: np.ndarray, pinned: bool) -> torch.cuda.Event:
         evt = torch.cuda.Event()
@@ -457,6 +634,7 @@ class _DeviceStager:
                     dst[: self._payload].copy_(
                         self._buf[: self._payload], non_blocking=False
                     )
+                self._drain_sums()
                 evt.record(self._stream)
             return evt
         # chunked fallback: serialize tensor copies through the small buffer.
@@ -479,6 +657,7 @@ class _DeviceStager:
                         dst[tm.offset + c0 : tm.offset + c1].copy_(
                             self._buf[: c1 - c0], non_blocking=pinned
                         )
+            self._drain_sums()
             evt.record(self._stream)
         self._stream.synchronize()
         self._pending = []

@@ -31,6 +31,9 @@ def main():
     p.add_argument("--seq", type=int, default=4096)
     p.add_argument("--ckpt-interval", type=int, default=50)
     p.add_argument("--ckpt-dir", default="/tmp/dlrover_amd_ckpt/llama")
+    p.add_argument("--ckpt-verify", action="store_true",
+                   help="checksum every checkpoint tensor inside the fused "
+                        "device snapshot and verify it on restore")
     p.add_argument("--progress-file", default="")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--grad-clip", type=float, default=0.0,
@@ -87,7 +90,9 @@ def main():
     opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=0.1, **clip_kw)
     trainer = ElasticTrainer(model)
 
-    cp = FsdpShardCheckpointer(args.ckpt_dir, model, opt)
+    cp = FsdpShardCheckpointer(
+        args.ckpt_dir, model, opt, checksum=True if args.ckpt_verify else None
+    )
     start_step = 0
     restored = cp.load_checkpoint()
     if restored is not None:

@@ -24,6 +24,7 @@ sources = [
     os.path.join(CSRC, "swiglu.hip"),
     os.path.join(CSRC, "adamw.hip"),
     os.path.join(CSRC, "multi_tensor.hip"),
+    os.path.join(CSRC, "ckpt_pack.hip"),
     os.path.join(CSRC, "softmax.hip"),
     os.path.join(CSRC, "cross_entropy.hip"),
     os.path.join(CSRC, "vocab_parallel_ce.hip"),
