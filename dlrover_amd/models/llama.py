@@ -41,7 +41,10 @@ class LlamaConfig:
     norm_eps: float = 1e-5
     tie_embeddings: bool = False
     # "auto": hand-written flash kernel on GPU when D==128 and S%64==0,
-    # composite (hipBLASLt GEMM + fused softmax) otherwise
+    # composite (hipBLASLt GEMM + fused softmax) otherwise. With a document
+    # mask (forward(..., doc_start=...)) the kernel needs S%256==0; "auto"
+    # falls back to the composite path with a plain masked fp32 softmax,
+    # "flash" raises ValueError on a shape the kernel cannot take
     attn_impl: str = "auto"
     # qkv projection bias (Qwen2-style checkpoints; Llama-3 uses none)
     attn_bias: bool = False
@@ -123,7 +126,9 @@ class Attention(nn.Module):
         )
         self.o_proj = nn.Linear(cfg.n_heads * hd, d, bias=False)
 
-    def forward(self, x, pos, cos, sin):
+    def forward(self, x, pos, cos, sin, doc_start=None):
+        """doc_start [B,S] int32 (optional): packed-sequence document mask —
+        token i attends j iff doc_start[b,i] <= j <= i."""
         cfg = self.cfg
         B, S, _ = x.shape
         hd, nh, nkv = cfg.head_dim, cfg.n_heads, cfg.n_kv_heads
@@ -140,6 +145,17 @@ class Attention(nn.Module):
             and hd == 128
             and S % 64 == 0
         )
+        if doc_start is not None and x.is_cuda and not (
+            hd == 128 and S % 256 == 0
+        ):
+            # the DOC kernels are the 256-row v3 ones only: "auto" takes the
+            # composite path, an explicit "flash" cannot be honoured
+            if cfg.attn_impl == "flash":
+                raise ValueError(
+                    "attn_impl='flash' with doc_start needs head_dim == 128 "
+                    f"and S % 256 == 0 (got head_dim={hd}, S={S})"
+                )
+            use_flash = False
         if use_flash:
             from dlrover_amd.ops import flash_attention
 
@@ -150,6 +166,7 @@ class Attention(nn.Module):
                 k.transpose(1, 2),
                 v.transpose(1, 2),
                 1.0 / math.sqrt(hd),
+                doc_start,
             )
             out = out.transpose(1, 2).reshape(B, S, nh * hd)
             return self.o_proj(out)
@@ -165,7 +182,20 @@ class Attention(nn.Module):
         scores = torch.matmul(q, k.transpose(-1, -2))  # [B,nkv,rep*S,S] MFMA
         # causal pattern: row r of the rep*S rows is query position r % S —
         # exactly the kernel's q_len=S row mapping
-        probs = causal_softmax(scores, scale=1.0 / math.sqrt(hd), q_len=S)
+        if doc_start is None:
+            probs = causal_softmax(scores, scale=1.0 / math.sqrt(hd), q_len=S)
+        else:
+            # document mask: a plain masked fp32 softmax (correct for every
+            # shape, but materialises the S^2 scores once more in fp32)
+            qpos = torch.arange(S, device=x.device).repeat(rep)  # [rep*S]
+            kpos = torch.arange(S, device=x.device)
+            first = doc_start.long().repeat(1, rep)  # [B, rep*S]
+            hidden = (kpos[None, None, None, :] > qpos[None, None, :, None]) | (
+                kpos[None, None, None, :] < first[:, None, :, None]
+            )
+            sf = (scores.float() / math.sqrt(hd)).masked_fill(
+                hidden, float("-inf"))
+            probs = torch.softmax(sf, dim=-1).to(scores.dtype)
         out = torch.matmul(probs, v)  # [B, nkv, rep*S, D] MFMA
         out = out.view(B, nkv, rep, S, hd).permute(0, 3, 1, 2, 4)
         out = out.reshape(B, S, nh * hd)
@@ -192,14 +222,14 @@ class Block(nn.Module):
         self.mlp_norm = RMSNorm(cfg.hidden_size, cfg.norm_eps)
         self.mlp = MLP(cfg)
 
-    def forward(self, x, pos, cos, sin, resid=None):
+    def forward(self, x, pos, cos, sin, resid=None, doc_start=None):
         """Two forms. Plain (resid=None): the classic pre-norm block.
         Residual-stream (resid given): x is the previous sublayer's BRANCH
         output (None on the first block); both residual adds fuse into the
         following RMSNorm kernel; returns (branch, resid). Must be entered
         through __call__ so FSDP's unshard hooks fire."""
         if resid is None:
-            x = x + self.attn(self.attn_norm(x), pos, cos, sin)
+            x = x + self.attn(self.attn_norm(x), pos, cos, sin, doc_start)
             x = x + self.mlp(self.mlp_norm(x))
             return x
         if x is None:
@@ -207,7 +237,7 @@ class Block(nn.Module):
         else:
             normed, resid = rmsnorm_add(x, resid, self.attn_norm.weight,
                                         self.attn_norm.eps)
-        a = self.attn(normed, pos, cos, sin)
+        a = self.attn(normed, pos, cos, sin, doc_start)
         normed, resid = rmsnorm_add(a, resid, self.mlp_norm.weight,
                                     self.mlp_norm.eps)
         return self.mlp(normed), resid
@@ -248,9 +278,22 @@ class LlamaForCausalLM(nn.Module):
         elif isinstance(m, nn.Embedding):
             nn.init.normal_(m.weight, std=0.02)
 
-    def forward(self, input_ids: torch.Tensor, labels: torch.Tensor = None):
+    def forward(self, input_ids: torch.Tensor, labels: torch.Tensor = None,
+                doc_start: torch.Tensor = None):
+        """doc_start [B,S] int32 (``dlrover_amd.ops.doc_start_from_ids`` /
+        ``doc_start_from_eos``): the sequences are packed from several
+        documents — attention stays inside a token's document and RoPE
+        positions restart at each document start. None: one document per
+        sequence, as before."""
         B, S = input_ids.shape
-        pos = torch.arange(S, device=input_ids.device, dtype=torch.int32)
+        if doc_start is None:
+            pos = torch.arange(S, device=input_ids.device, dtype=torch.int32)
+        else:
+            from dlrover_amd.ops import doc_positions
+
+            doc_start = doc_start.to(device=input_ids.device,
+                                     dtype=torch.int32).contiguous()
+            pos = doc_positions(doc_start)  # [B, S]
         x = self.embed(input_ids)
         ckpt = (self.cfg.activation_checkpointing and self.training
                 and torch.is_grad_enabled())
@@ -263,13 +306,15 @@ class LlamaForCausalLM(nn.Module):
             for blk in self.blocks:
                 if ckpt:
                     branch, resid = checkpoint(
-                        lambda b, r, _blk=blk: _blk(
-                            b, pos, self.rope_cos, self.rope_sin, resid=r),
-                        branch, resid, use_reentrant=False,
+                        lambda b, r, ds, _blk=blk: _blk(
+                            b, pos, self.rope_cos, self.rope_sin, resid=r,
+                            doc_start=ds),
+                        branch, resid, doc_start, use_reentrant=False,
                     )
                 else:
                     branch, resid = blk(
-                        branch, pos, self.rope_cos, self.rope_sin, resid=resid
+                        branch, pos, self.rope_cos, self.rope_sin, resid=resid,
+                        doc_start=doc_start,
                     )
             x, _ = rmsnorm_add(branch, resid, self.final_norm.weight,
                                self.final_norm.eps)
@@ -277,12 +322,14 @@ class LlamaForCausalLM(nn.Module):
             for blk in self.blocks:
                 if ckpt:
                     x = checkpoint(
-                        lambda h, _blk=blk: _blk(
-                            h, pos, self.rope_cos, self.rope_sin),
-                        x, use_reentrant=False,
+                        lambda h, ds, _blk=blk: _blk(
+                            h, pos, self.rope_cos, self.rope_sin,
+                            doc_start=ds),
+                        x, doc_start, use_reentrant=False,
                     )
                 else:
-                    x = blk(x, pos, self.rope_cos, self.rope_sin)
+                    x = blk(x, pos, self.rope_cos, self.rope_sin,
+                            doc_start=doc_start)
             x = self.final_norm(x)
         logits = self.lm_head(x)
         if labels is None:

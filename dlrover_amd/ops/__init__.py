@@ -15,7 +15,13 @@ from dlrover_amd.ops.api import (  # noqa: F401
     ce_shard_finish,
     ce_shard_stats,
     flash_attention,
+    flash_attention_ref,
+    flash_attention_supports_doc_mask,
     cross_entropy_loss,
+    doc_end_from_start,
+    doc_positions,
+    doc_start_from_eos,
+    doc_start_from_ids,
     fused_adamw_multi_step,
     fused_adamw_step,
     grad_sq_norm,
@@ -23,8 +29,10 @@ from dlrover_amd.ops.api import (  # noqa: F401
     hip_ops_available,
     rmsnorm,
     rmsnorm_add,
+    rope_ref,
     rope_rotate,
     swiglu,
+    validate_doc_start,
     vocab_parallel_cross_entropy,
 )
 from dlrover_amd.ops.adamw import FusedAdamW  # noqa: F401

@@ -67,11 +67,18 @@ def swiglu_ref(gate_up: torch.Tensor) -> torch.Tensor:
 def rope_ref(
     x: torch.Tensor, pos: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor
 ) -> torch.Tensor:
-    """x [..., n_heads, D]; pos [n_tokens]; cos/sin [max_pos, D/2] fp32."""
+    """x [..., n_tokens, n_heads, D]; cos/sin [max_pos, D/2] fp32. pos is
+    [n_tokens] (one vector shared by every leading index), or one position
+    per token of x: [B, S] for x [B, S, n_heads, D], or the same flattened to
+    [B*S] (the form the HIP kernel takes)."""
     d = x.shape[-1]
     xf = x.float()
     x1, x2 = xf[..., : d // 2], xf[..., d // 2 :]
-    shape = [1] * (x.dim() - 3) + [-1, 1, d // 2]
+    if pos.dim() == 1 and (x.dim() < 3 or pos.numel() == x.shape[-3]):
+        shape = [1] * (x.dim() - 3) + [-1, 1, d // 2]
+    else:
+        shape = list(x.shape[:-2]) + [1, d // 2]
+        pos = pos.reshape(-1)
     c = cos[pos].view(*shape)
     s = sin[pos].view(*shape)
     o1 = x1 * c - x2 * s
@@ -304,16 +311,117 @@ def causal_softmax(
     return _CausalSoftmax.apply(scores, scale, q_offset, q_len)
 
 
-def flash_attention_ref(
-    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float
+# ---------------------------------------------------------------------------
+# document masks for packed sequences
+#
+# One int32 tensor doc_start[B, S]: entry [b, i] is the index of the first
+# token of the document that holds position i. Invariants: non-decreasing
+# along i, 0 <= doc_start[b, i] <= i, and constant within a document
+# (doc_start[b, doc_start[b, i]] == doc_start[b, i]). Query i attends key j
+# iff doc_start[b, i] <= j <= i, so every row sees at least itself.
+# ---------------------------------------------------------------------------
+
+
+def validate_doc_start(doc_start: torch.Tensor) -> None:
+    """Raise ValueError unless doc_start [B, S] keeps the invariants above.
+    Reads the answer on the host: one device sync."""
+    if doc_start.dim() != 2:
+        raise ValueError("doc_start must be [B, S]")
+    ds = doc_start.long()
+    S = ds.shape[1]
+    idx = torch.arange(S, device=ds.device).expand_as(ds)
+    in_range = (ds >= 0) & (ds <= idx)
+    monotone = ds[:, 1:] >= ds[:, :-1]
+    # a document starts where its start points (gather only at clamped indices)
+    own = ds.gather(1, ds.clamp(0, S - 1)) == ds
+    ok = torch.stack([in_range.all(), monotone.all(), own.all()]).tolist()
+    if not ok[0]:
+        raise ValueError("doc_start: need 0 <= doc_start[b, i] <= i")
+    if not ok[1]:
+        raise ValueError("doc_start: must be non-decreasing along the sequence")
+    if not ok[2]:
+        raise ValueError("doc_start: must point at the first token of a document")
+
+
+def _doc_start_from_new(new: torch.Tensor, validate: bool) -> torch.Tensor:
+    """new [B, S] bool, True where a document begins (column 0 always does)."""
+    S = new.shape[1]
+    idx = torch.arange(S, device=new.device, dtype=torch.int32).expand_as(new)
+    start = torch.where(new, idx, torch.zeros_like(idx))
+    out = torch.cummax(start, dim=1).values.contiguous()
+    if validate:
+        validate_doc_start(out)
+    return out
+
+
+def doc_start_from_ids(doc_ids: torch.Tensor, validate: bool = False) -> torch.Tensor:
+    """doc_start [B, S] (int32) from per-token document ids [B, S]: a new
+    document begins wherever the id changes. Pure torch, no host sync unless
+    ``validate``."""
+    new = torch.ones_like(doc_ids, dtype=torch.bool)
+    new[:, 1:] = doc_ids[:, 1:] != doc_ids[:, :-1]
+    return _doc_start_from_new(new, validate)
+
+
+def doc_start_from_eos(
+    tokens: torch.Tensor, eos_id: int, validate: bool = False
 ) -> torch.Tensor:
-    """fp32 composite reference: q [B,H,S,D], k/v [B,HKV,S,D], causal."""
+    """doc_start [B, S] (int32) from token ids [B, S]: an EOS token ends its
+    document and the next token starts a new one (an EOS in the last position
+    starts nothing). Pure torch, no host sync unless ``validate``."""
+    new = torch.ones_like(tokens, dtype=torch.bool)
+    new[:, 1:] = tokens[:, :-1] == eos_id
+    return _doc_start_from_new(new, validate)
+
+
+def doc_positions(doc_start: torch.Tensor) -> torch.Tensor:
+    """Position of every token inside its own document: arange(S) - doc_start,
+    int32 [B, S] — the RoPE positions of a packed batch."""
+    S = doc_start.shape[1]
+    idx = torch.arange(S, device=doc_start.device, dtype=torch.int32)
+    return (idx - doc_start.int()).contiguous()
+
+
+def doc_end_from_start(doc_start: torch.Tensor) -> torch.Tensor:
+    """doc_end [B, S] (int32): the exclusive end of the document holding each
+    position, i.e. the next larger doc_start value, or S. Key j is visible to
+    exactly the queries j <= i < doc_end[b, j] — the bound the kv-major
+    backward kernels need. Torch ops on doc_start's device, no host sync."""
+    ds = doc_start.int()
+    B, S = ds.shape
+    idx = torch.arange(S, device=ds.device, dtype=torch.int32).expand(B, S)
+    # where a document begins its start is its own index; elsewhere "none yet"
+    nxt = torch.where(ds == idx, idx, torch.full_like(idx, S))
+    # doc_end[i] = min over j > i of nxt[j] (or S): a reversed running minimum
+    shifted = torch.cat([nxt[:, 1:], torch.full_like(idx[:, :1], S)], dim=1)
+    return torch.cummin(shifted.flip(1), dim=1).values.flip(1).contiguous()
+
+
+def flash_attention_supports_doc_mask(q: torch.Tensor) -> bool:
+    """True when the document-masked HIP kernels can take q [B,H,S,D]: on the
+    GPU, D == 128 and S % 256 == 0 (the 32x32-MFMA kernels' shapes)."""
+    return bool(q.is_cuda and q.shape[-1] == 128 and q.shape[-2] % 256 == 0)
+
+
+def flash_attention_ref(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    scale: float,
+    doc_start: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """fp32 composite reference: q [B,H,S,D], k/v [B,HKV,S,D], causal; with
+    doc_start [B,S] additionally restricted to the query's own document."""
     B, H, S, D = q.shape
     rep = H // k.shape[1]
     kf = k.float().repeat_interleave(rep, 1)
     vf = v.float().repeat_interleave(rep, 1)
     s_ = torch.matmul(q.float(), kf.transpose(-1, -2)) * scale
     mask = torch.triu(torch.ones(S, S, dtype=torch.bool, device=q.device), 1)
+    if doc_start is not None:
+        kpos = torch.arange(S, device=q.device)
+        # [B, 1, S(q), S(k)]: keys before the query's document
+        mask = mask | (kpos[None, None, None, :] < doc_start.long()[:, None, :, None])
     s_ = s_.masked_fill(mask, float("-inf"))
     p = torch.softmax(s_, -1)
     return torch.matmul(p, vf).to(q.dtype)
@@ -321,7 +429,8 @@ def flash_attention_ref(
 
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale):
+    def forward(ctx, q, k, v, scale, doc_start=None):
+        ctx.has_doc = doc_start is not None
         if _use_hip(q):
             # strided [B,H,S,D] views are fine (kernels are stride-aware);
             # only the head dim must be contiguous
@@ -331,8 +440,20 @@ class _FlashAttention(torch.autograd.Function):
                 k = k.contiguous()
             if v.stride(-1) != 1:
                 v = v.contiguous()
-            out, lse = hip_ops().flash_attn_fwd(q, k, v, scale)
-            ctx.save_for_backward(q, k, v, out, lse)
+            if doc_start is not None:
+                if not flash_attention_supports_doc_mask(q):
+                    raise ValueError(
+                        "flash_attention: doc_start needs D == 128 and "
+                        f"S % 256 == 0 on the GPU, got D={q.shape[-1]} "
+                        f"S={q.shape[-2]}"
+                    )
+                ds = doc_start.to(device=q.device, dtype=torch.int32).contiguous()
+                de = doc_end_from_start(ds)
+                out, lse = hip_ops().flash_attn_doc_fwd(q, k, v, scale, ds)
+                ctx.save_for_backward(q, k, v, out, lse, ds, de)
+            else:
+                out, lse = hip_ops().flash_attn_fwd(q, k, v, scale)
+                ctx.save_for_backward(q, k, v, out, lse)
             ctx.scale = scale
             ctx.use_hip = True
             return out
@@ -341,30 +462,49 @@ class _FlashAttention(torch.autograd.Function):
         k32 = k.detach().clone().requires_grad_(True)
         v32 = v.detach().clone().requires_grad_(True)
         with torch.enable_grad():
-            out = flash_attention_ref(q32, k32, v32, scale)
+            out = flash_attention_ref(q32, k32, v32, scale, doc_start)
         ctx.saved_ref = (q32, k32, v32, out)
         return out.detach()
 
     @staticmethod
     def backward(ctx, dout):
         if ctx.use_hip:
+            if ctx.has_doc:
+                q, k, v, out, lse, ds, de = ctx.saved_tensors
+                dq, dk, dv = hip_ops().flash_attn_doc_bwd(
+                    q, k, v, out, dout.contiguous(), lse, ctx.scale, ds, de
+                )
+                return dq, dk, dv, None, None
             q, k, v, out, lse = ctx.saved_tensors
             dq, dk, dv = hip_ops().flash_attn_bwd(
                 q, k, v, out, dout.contiguous(), lse, ctx.scale
             )
-            return dq, dk, dv, None
+            return dq, dk, dv, None, None
         q32, k32, v32, out = ctx.saved_ref
         torch.autograd.backward(out, dout)
-        return q32.grad, k32.grad, v32.grad, None
+        return q32.grad, k32.grad, v32.grad, None, None
 
 
 def flash_attention(
-    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    scale: float,
+    doc_start: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Fused causal GQA attention. q [B,H,S,D], k/v [B,HKV,S,D], D=128,
     S % 64 == 0. Never materializes the S^2 score matrix (hand-written MFMA
-    kernels, ops/csrc/attention*.hip)."""
-    return _FlashAttention.apply(q, k, v, scale)
+    kernels, ops/csrc/attention*.hip).
+
+    doc_start [B,S] (int32, see ``doc_start_from_ids`` / ``_from_eos``) adds
+    the document mask of packed sequences: query i attends key j iff
+    doc_start[b,i] <= j <= i. On the GPU that is the DOC variant of the v3
+    kernels (D == 128, S % 256 == 0 — ``flash_attention_supports_doc_mask``;
+    other shapes raise ValueError), which also skips the K/V tiles outside a
+    block's documents. ``None`` is the causal path, unchanged."""
+    if doc_start is None:
+        return _FlashAttention.apply(q, k, v, scale)
+    return _FlashAttention.apply(q, k, v, scale, doc_start)
 
 
 class _CrossEntropy(torch.autograd.Function):

@@ -92,6 +92,12 @@ __device__ __forceinline__ void pairswap_frags(const float v16[16], int half,
 // dQ kernel
 // ---------------------------------------------------------------------------
 
+// DOC=true: the document mask of attention_v3.hip (query i sees key j iff
+// doc_start[b][i] <= j <= i). The q-major dQ kernel takes doc_start like the
+// forward; the kv-major dV/dK kernels take doc_end[b][j], the exclusive end
+// of the document holding key j: key j is seen by exactly the queries
+// j <= i < doc_end[b][j]. DOC=false is the causal code; neither is read.
+template <bool DOC>
 __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
@@ -100,7 +106,8 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
     long long qs_b, long long qs_h, long long qs_s,
     long long ks_b, long long ks_h, long long ks_s,
     long long vs_b, long long vs_h, long long vs_s,
-    long long ds_b, long long ds_h, long long ds_s) {
+    long long ds_b, long long ds_h, long long ds_s,
+    const int* __restrict__ doc_start) {
   __shared__ char k_lds[2][FB_T * FB_D * 2];  // 2 x 16 KB, row-major swz
   __shared__ char v_lds[2][FB_T * FB_D * 2];  // 2 x 16 KB, row-major swz
 
@@ -173,18 +180,29 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
   const int n_tiles = (qt + 1) * (FB_QB / FB_T);
   const int wave_q_max = qt * FB_QB + wave * 32 + 31;
 
-  issue_loads(0);
+  // DOC: per-lane first visible key (clamped into [0, q_glob]), the wave's
+  // smallest (its first row's) and the block-uniform first tile — as in the
+  // forward kernel
+  int ds_lane = 0, wave_ds_min = 0, kt0 = 0;
+  if (DOC) {
+    const int* ds_row = doc_start + (long long)b * S;
+    ds_lane = min(max(ds_row[q_glob], 0), q_glob);
+    wave_ds_min = __builtin_amdgcn_readfirstlane(ds_lane);
+    kt0 = min(max(ds_row[qt * FB_QB], 0) / FB_T, qt * (FB_QB / FB_T));
+  }
+
+  issue_loads(kt0);
   write_lds(0);
   __syncthreads();
 
-  for (int kt = 0; kt < n_tiles; ++kt) {
-    const int cur = kt & 1;
+  for (int kt = kt0; kt < n_tiles; ++kt) {
+    const int cur = (kt - kt0) & 1;  // tile kt0 sits in buffer 0
     const char* k_cur = k_lds[cur];
     const char* v_cur = v_lds[cur];
     if (kt + 1 < n_tiles) issue_loads(kt + 1);
 
     const int kv0 = kt * FB_T;
-    if (kv0 <= wave_q_max) {
+    if (kv0 <= wave_q_max && (!DOC || kv0 + FB_T - 1 >= wave_ds_min)) {
       // per kv-subtile of 32: S^T -> P^T -> dP^T -> dS^T frags, one
       // accumulator pair live at a time (register pressure: the 2-subtile
       // batched version spilled 26 VGPRs)
@@ -206,8 +224,9 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int kv_glob = kv0 + n * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          acc_s[r] =
-              (kv_glob > q_glob) ? 0.f : __expf(acc_s[r] * scale - L);
+          acc_s[r] = (kv_glob > q_glob || (DOC && kv_glob < ds_lane))
+                         ? 0.f
+                         : __expf(acc_s[r] * scale - L);
         }
         // dP^T = V dO^T
         f32x16_t acc_dp;
@@ -291,7 +310,9 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
 // ---------------------------------------------------------------------------
 
 // shared prologue macro for the two kv-major kernels
-#define FB_DKV_PROLOGUE()                                                    \
+// (NEED_D: only the dK kernel reads Dvec; the dV kernel must not touch
+// d_lds at all, or the array stays allocated in its LDS)
+#define FB_DKV_PROLOGUE(NEED_D)                                              \
   __shared__ char q_lds[FB_T * FB_D * 2];                                    \
   __shared__ char do_lds[FB_T * FB_D * 2];                                   \
   __shared__ float l_lds[FB_T];                                              \
@@ -315,7 +336,19 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
       *reinterpret_cast<const bf16x8*>(k_head + (long long)kv_own * ks_s +   \
                                        ks * 16 + half * 8);                  \
   const int qt_min = kvb0 / FB_T;                                            \
-  const int n_qt = S / FB_T - qt_min;                                        \
+  /* DOC: de_lane = exclusive end of this lane's kv row's document, clamped  \
+     into (kv_own, S]; only compared, never an address. vis_len = how many   \
+     q rows from kv_own on see this row, so the whole element mask is ONE    \
+     unsigned compare (q - kv_own) < vis_len. wave_q_end / q_end: the last   \
+     lane's / last row's value is the wave's / block's largest (doc_end is   \
+     non-decreasing). q_end is block-uniform, so it may shrink n_qt. */      \
+  const int* de_row = DOC ? doc_end + (long long)b * S : nullptr;            \
+  const int de_lane = DOC ? min(max(de_row[kv_own], kv_own + 1), S) : S;     \
+  const unsigned vis_len = (unsigned)(de_lane - kv_own);                     \
+  const int wave_q_end = DOC ? __builtin_amdgcn_readlane(de_lane, 31) : S;   \
+  const int q_end =                                                          \
+      DOC ? min(max(de_row[kvb0 + FB_QB - 1], kvb0 + 1), S) : S;             \
+  const int n_qt = (DOC ? (q_end + FB_T - 1) / FB_T : S / FB_T) - qt_min;    \
   const int n_work = rep * n_qt;                                             \
   const int wave_kv_min = kvb0 + wave * 32;                                  \
   auto stage_qdo = [&](int h, int qt) {                                      \
@@ -337,10 +370,11 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
     if (tid < FB_T) {                                                        \
       const long long lrow = ((long long)b * H + h) * S + qt * FB_T + tid;   \
       l_lds[tid] = lse[lrow];                                                \
-      d_lds[tid] = dvec[lrow];                                               \
+      if (NEED_D) d_lds[tid] = dvec[lrow];                                   \
     }                                                                        \
   }
 
+template <bool DOC>
 __global__ __launch_bounds__(512) void fa_bwd_dv_v3_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
@@ -350,8 +384,9 @@ __global__ __launch_bounds__(512) void fa_bwd_dv_v3_kernel(
     long long qs_b, long long qs_h, long long qs_s,
     long long ks_b, long long ks_h, long long ks_s,
     long long vs_b, long long vs_h, long long vs_s,
-    long long ds_b, long long ds_h, long long ds_s) {
-  FB_DKV_PROLOGUE();
+    long long ds_b, long long ds_h, long long ds_s,
+    const int* __restrict__ doc_end) {
+  FB_DKV_PROLOGUE(false);
 
   // ---------------- pass 1: dV^T = dO^T P ----------------
   {
@@ -368,10 +403,13 @@ __global__ __launch_bounds__(512) void fa_bwd_dv_v3_kernel(
       stage_qdo(h, qt);
       __syncthreads();
       if (qt * FB_T + FB_T - 1 < wave_kv_min) continue;  // fully masked
+      // DOC: a q tile at or past the end of the wave's last document
+      if (DOC && qt * FB_T >= wave_q_end) continue;
 #pragma unroll
       for (int st = 0; st < 2; ++st) {  // q subtiles of 32
         const int q0 = qt * FB_T + st * 32;
         if (q0 + 31 < wave_kv_min) continue;
+        if (DOC && q0 >= wave_q_end) continue;
         // S = Q K^T (C col = kv own, rows = q)
         f32x16_t acc_s;
 #pragma unroll
@@ -392,7 +430,9 @@ __global__ __launch_bounds__(512) void fa_bwd_dv_v3_kernel(
         for (int r = 0; r < 16; ++r) {
           const int qrow = st * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
           const int q_glob = qt * FB_T + qrow;
-          pv[r] = (kv_own > q_glob)
+          const bool masked = DOC ? (unsigned)(q_glob - kv_own) >= vis_len
+                                  : kv_own > q_glob;
+          pv[r] = masked
                       ? 0.f
                       : __expf(acc_s[r] * scale - l_lds[qrow]);
         }
@@ -425,6 +465,7 @@ __global__ __launch_bounds__(512) void fa_bwd_dv_v3_kernel(
 
 }
 
+template <bool DOC>
 __global__ __launch_bounds__(512) void fa_bwd_dk_v3_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
@@ -434,8 +475,9 @@ __global__ __launch_bounds__(512) void fa_bwd_dk_v3_kernel(
     long long qs_b, long long qs_h, long long qs_s,
     long long ks_b, long long ks_h, long long ks_s,
     long long vs_b, long long vs_h, long long vs_s,
-    long long ds_b, long long ds_h, long long ds_s) {
-  FB_DKV_PROLOGUE();
+    long long ds_b, long long ds_h, long long ds_s,
+    const int* __restrict__ doc_end) {
+  FB_DKV_PROLOGUE(true);
   const short* v_head = v + (long long)b * vs_b + (long long)g * vs_h;
   // persistent V row (B-operand for dP = dO V^T)
   bf16x8 bv[8];
@@ -459,10 +501,12 @@ __global__ __launch_bounds__(512) void fa_bwd_dk_v3_kernel(
       stage_qdo(h, qt);
       __syncthreads();
       if (qt * FB_T + FB_T - 1 < wave_kv_min) continue;
+      if (DOC && qt * FB_T >= wave_q_end) continue;
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
         const int q0 = qt * FB_T + st * 32;
         if (q0 + 31 < wave_kv_min) continue;
+        if (DOC && q0 >= wave_q_end) continue;
         // S = Q K^T and dP = dO V^T in ONE interleaved k-loop (separate
         // 8-deep unrolled loops kept too many LDS-read temporaries live:
         // 62 VGPR spills)
@@ -488,7 +532,9 @@ __global__ __launch_bounds__(512) void fa_bwd_dk_v3_kernel(
         for (int r = 0; r < 16; ++r) {
           const int qrow = st * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
           const int q_glob = qt * FB_T + qrow;
-          const float p = (kv_own > q_glob)
+          const bool masked = DOC ? (unsigned)(q_glob - kv_own) >= vis_len
+                                  : kv_own > q_glob;
+          const float p = masked
                               ? 0.f
                               : __expf(acc_s[r] * scale - l_lds[qrow]);
           dsv[r] = p * (acc_dp[r] - d_lds[qrow]) * scale;
@@ -518,6 +564,31 @@ __global__ __launch_bounds__(512) void fa_bwd_dk_v3_kernel(
   }
 }
 
+template <bool DOC>
+static void dkv_v3_launch(const void* q, const void* k, const void* v,
+                          const void* dout, const void* lse, const void* dvec,
+                          void* dk32, void* dv32, int B, int H, int HKV, int S,
+                          float scale, const long long* strides,
+                          const int* doc_end, hipStream_t stream) {
+  const int kv_blocks = S / FB_QB;
+  // chunk (head, q-tile) work across gridDim.y until the launch fills the
+  // 256-CU chip (each block is CU-wide: 512 threads, 1 block/CU)
+  int ch = 1;
+  while (kv_blocks * ch * B * HKV < 512 && ch < 16) ch <<= 1;
+  dim3 grid(kv_blocks, ch, B * HKV);
+#define FB_DKV_LAUNCH_ARGS                                                   \
+  (const short*)q, (const short*)k, (const short*)v, (const short*)dout,     \
+      (const float*)lse, (const float*)dvec, (float*)dk32, (float*)dv32, B,  \
+      H, HKV, S, scale, strides[0], strides[1], strides[2], strides[3],      \
+      strides[4], strides[5], strides[6], strides[7], strides[8],            \
+      strides[9], strides[10], strides[11]
+  hipLaunchKernelGGL(fa_bwd_dv_v3_kernel<DOC>, grid, dim3(512), 0, stream,
+                     FB_DKV_LAUNCH_ARGS, doc_end);
+  hipLaunchKernelGGL(fa_bwd_dk_v3_kernel<DOC>, grid, dim3(512), 0, stream,
+                     FB_DKV_LAUNCH_ARGS, doc_end);
+#undef FB_DKV_LAUNCH_ARGS
+}
+
 extern "C" void fa_bwd_dkv_v3_launch(const void* q, const void* k,
                                      const void* v, const void* dout,
                                      const void* lse, const void* dvec,
@@ -525,28 +596,18 @@ extern "C" void fa_bwd_dkv_v3_launch(const void* q, const void* k,
                                      int HKV, int S, float scale,
                                      const long long* strides,
                                      hipStream_t stream) {
-  const int kv_blocks = S / FB_QB;
-  // chunk (head, q-tile) work across gridDim.y until the launch fills the
-  // 256-CU chip (each block is CU-wide: 512 threads, 1 block/CU)
-  int ch = 1;
-  while (kv_blocks * ch * B * HKV < 512 && ch < 16) ch <<= 1;
-  dim3 grid(kv_blocks, ch, B * HKV);
-  hipLaunchKernelGGL(fa_bwd_dv_v3_kernel, grid, dim3(512), 0, stream,
-                     (const short*)q, (const short*)k, (const short*)v,
-                     (const short*)dout, (const float*)lse,
-                     (const float*)dvec, (float*)dk32, (float*)dv32, B, H,
-                     HKV, S, scale, strides[0], strides[1], strides[2],
-                     strides[3], strides[4], strides[5], strides[6],
-                     strides[7], strides[8], strides[9], strides[10],
-                     strides[11]);
-  hipLaunchKernelGGL(fa_bwd_dk_v3_kernel, grid, dim3(512), 0, stream,
-                     (const short*)q, (const short*)k, (const short*)v,
-                     (const short*)dout, (const float*)lse,
-                     (const float*)dvec, (float*)dk32, (float*)dv32, B, H,
-                     HKV, S, scale, strides[0], strides[1], strides[2],
-                     strides[3], strides[4], strides[5], strides[6],
-                     strides[7], strides[8], strides[9], strides[10],
-                     strides[11]);
+  dkv_v3_launch<false>(q, k, v, dout, lse, dvec, dk32, dv32, B, H, HKV, S,
+                       scale, strides, nullptr, stream);
+}
+
+// document-masked variant: doc_end is int32 [B, S], contiguous
+extern "C" void fa_bwd_dkv_v3_doc_launch(
+    const void* q, const void* k, const void* v, const void* dout,
+    const void* lse, const void* dvec, void* dk32, void* dv32, int B, int H,
+    int HKV, int S, float scale, const long long* strides,
+    const void* doc_end, hipStream_t stream) {
+  dkv_v3_launch<true>(q, k, v, dout, lse, dvec, dk32, dv32, B, H, HKV, S,
+                      scale, strides, (const int*)doc_end, stream);
 }
 
 extern "C" void fa_bwd_dq_v3_launch(const void* q, const void* k,
@@ -556,11 +617,29 @@ extern "C" void fa_bwd_dq_v3_launch(const void* q, const void* k,
                                     float scale, const long long* strides,
                                     hipStream_t stream) {
   dim3 grid(S / FB_QB, H, B);
-  hipLaunchKernelGGL(fa_bwd_dq_v3_kernel, grid, dim3(512), 0, stream,
+  hipLaunchKernelGGL(fa_bwd_dq_v3_kernel<false>, grid, dim3(512), 0, stream,
                      (const short*)q, (const short*)k, (const short*)v,
                      (const short*)dout, (const float*)lse,
                      (const float*)dvec, (short*)dq, B, H, HKV, S, scale,
                      strides[0], strides[1], strides[2], strides[3],
                      strides[4], strides[5], strides[6], strides[7],
-                     strides[8], strides[9], strides[10], strides[11]);
+                     strides[8], strides[9], strides[10], strides[11],
+                     nullptr);
+}
+
+// document-masked variant: doc_start is int32 [B, S], contiguous
+extern "C" void fa_bwd_dq_v3_doc_launch(
+    const void* q, const void* k, const void* v, const void* dout,
+    const void* lse, const void* dvec, void* dq, int B, int H, int HKV, int S,
+    float scale, const long long* strides, const void* doc_start,
+    hipStream_t stream) {
+  dim3 grid(S / FB_QB, H, B);
+  hipLaunchKernelGGL(fa_bwd_dq_v3_kernel<true>, grid, dim3(512), 0, stream,
+                     (const short*)q, (const short*)k, (const short*)v,
+                     (const short*)dout, (const float*)lse,
+                     (const float*)dvec, (short*)dq, B, H, HKV, S, scale,
+                     strides[0], strides[1], strides[2], strides[3],
+                     strides[4], strides[5], strides[6], strides[7],
+                     strides[8], strides[9], strides[10], strides[11],
+                     (const int*)doc_start);
 }

@@ -83,7 +83,15 @@ __device__ __forceinline__ bf16x8 tr_colT_frag(const char* lds, int rb,
 //   measured bank-conflict source) and PV A-operand read b128.
 // TRV=true ("v4"): V staged ROW-major like K (conflict-free b128 writes) and
 //   the V^T A-operand gathered with ds_read_b64_tr_b16 (tr_colT_frag).
-template <bool TRV>
+//
+// DOC=true ("document mask", packed sequences): query i attends key j iff
+//   doc_start[b][i] <= j <= i. Same MFMA sequence, LDS layout and staging; the
+//   variant is one more comparison per score against a per-lane scalar, a
+//   block-uniform first tile kt0 and a per-wave skip of tiles that end before
+//   the wave's first document. Everything read from doc_start is clamped, so
+//   arbitrary int32 content can give wrong numbers but never a bad address.
+//   DOC=false is the causal kernel: doc_start is never read.
+template <bool TRV, bool DOC>
 __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, short* __restrict__ out,
@@ -91,7 +99,8 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
     long long qs_b, long long qs_h, long long qs_s,
     long long ks_b, long long ks_h, long long ks_s,
     long long vs_b, long long vs_h, long long vs_s,
-    long long os_b, long long os_h, long long os_s) {
+    long long os_b, long long os_h, long long os_s,
+    const int* __restrict__ doc_start) {
   __shared__ char k_lds[2][FA3_KT * FA3_D * 2];   // 2 x 16 KB
   __shared__ char vt_lds[2][FA3_D * FA3_KT * 2];  // 2 x 16 KB
 
@@ -179,18 +188,35 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
   // this wave's last needed tile (q rows < its band contribute nothing)
   const int wave_q_max = qt * FA3_QB + wave * FA3_QW + FA3_QW - 1;
 
-  issue_loads(0);
+  // DOC: ds_lane = first key this lane's q row may see, clamped into
+  // [0, q_glob] so every row keeps its diagonal element. wave_ds_min is the
+  // wave's first row's value (the smallest: doc_start is non-decreasing).
+  // kt0 = tile of the block's first row's document start — block-uniform, so
+  // it may move the loop start; clamped to the block's first diagonal tile.
+  int ds_lane = 0, wave_ds_min = 0, kt0 = 0;
+  if (DOC) {
+    const int* ds_row = doc_start + (long long)b * S;
+    ds_lane = min(max(ds_row[q_glob], 0), q_glob);
+    wave_ds_min = __builtin_amdgcn_readfirstlane(ds_lane);
+    kt0 = min(max(ds_row[qt * FA3_QB], 0) / FA3_KT,
+              qt * (FA3_QB / FA3_KT));
+  }
+
+  issue_loads(kt0);
   write_lds(0);
   __syncthreads();
 
-  for (int kt = 0; kt < n_tiles; ++kt) {
-    const int cur = kt & 1;
+  for (int kt = kt0; kt < n_tiles; ++kt) {
+    const int cur = (kt - kt0) & 1;  // tile kt0 sits in buffer 0
     const char* k_cur = k_lds[cur];
     const char* vt_cur = vt_lds[cur];
     if (kt + 1 < n_tiles) issue_loads(kt + 1);  // T14: issue early
 
     const int kv0 = kt * FA3_KT;
-    const bool wave_active = kv0 <= wave_q_max;
+    // per-wave skip (between the barriers, never across one): tiles above
+    // the wave's band and, DOC, tiles that end before its first document
+    const bool wave_active =
+        kv0 <= wave_q_max && (!DOC || kv0 + FA3_KT - 1 >= wave_ds_min);
 
     if (wave_active) {
       // ---- S^T tile: two 32x32 outputs (kv subtiles), K=128 ----
@@ -226,7 +252,12 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
           const int kv_glob =
               kv0 + n * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
           float s = acc_s[n][r] * scale;
-          if (kv_glob > q_glob) s = -1e30f;
+          // DOC: a tile can be fully masked for a row whose document starts
+          // later than the wave's first row's. The -1e30 sentinel then gives
+          // exp(0) = 1 per element into l_run/acc_o; the row's first real
+          // score (its diagonal at the latest) wipes that: alpha =
+          // exp(-1e30 - m) = 0.
+          if (kv_glob > q_glob || (DOC && kv_glob < ds_lane)) s = -1e30f;
           acc_s[n][r] = s;
           pmax = fmaxf(pmax, s);
         }
@@ -372,11 +403,11 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
   }
 }
 
-extern "C" void flash_attn_fwd_v3_launch(const void* q, const void* k,
-                                         const void* v, void* out, void* lse,
-                                         int B, int H, int HKV, int S,
-                                         float scale, const long long* strides,
-                                         hipStream_t stream) {
+template <bool DOC>
+static void fwd_v3_launch(const void* q, const void* k, const void* v,
+                          void* out, void* lse, int B, int H, int HKV, int S,
+                          float scale, const long long* strides,
+                          const int* doc_start, hipStream_t stream) {
   dim3 grid(S / FA3_QB, H, B);
   // v4 (tr-read V, conflict-free staging) unless DLROVER_FA_TRV=0
   static const bool trv = []() {
@@ -384,20 +415,38 @@ extern "C" void flash_attn_fwd_v3_launch(const void* q, const void* k,
     return e == nullptr || e[0] != '0';
   }();
   if (trv) {
-    hipLaunchKernelGGL((flash_attn_fwd_v3_kernel<true>), grid, dim3(512), 0,
-                       stream, (const short*)q, (const short*)k,
+    hipLaunchKernelGGL((flash_attn_fwd_v3_kernel<true, DOC>), grid, dim3(512),
+                       0, stream, (const short*)q, (const short*)k,
                        (const short*)v, (short*)out, (float*)lse, B, H, HKV,
                        S, scale, strides[0], strides[1], strides[2],
                        strides[3], strides[4], strides[5], strides[6],
                        strides[7], strides[8], strides[9], strides[10],
-                       strides[11]);
+                       strides[11], doc_start);
   } else {
-    hipLaunchKernelGGL((flash_attn_fwd_v3_kernel<false>), grid, dim3(512), 0,
-                       stream, (const short*)q, (const short*)k,
+    hipLaunchKernelGGL((flash_attn_fwd_v3_kernel<false, DOC>), grid,
+                       dim3(512), 0, stream, (const short*)q, (const short*)k,
                        (const short*)v, (short*)out, (float*)lse, B, H, HKV,
                        S, scale, strides[0], strides[1], strides[2],
                        strides[3], strides[4], strides[5], strides[6],
                        strides[7], strides[8], strides[9], strides[10],
-                       strides[11]);
+                       strides[11], doc_start);
   }
+}
+
+extern "C" void flash_attn_fwd_v3_launch(const void* q, const void* k,
+                                         const void* v, void* out, void* lse,
+                                         int B, int H, int HKV, int S,
+                                         float scale, const long long* strides,
+                                         hipStream_t stream) {
+  fwd_v3_launch<false>(q, k, v, out, lse, B, H, HKV, S, scale, strides,
+                       nullptr, stream);
+}
+
+// document-masked variant: doc_start is int32 [B, S], contiguous
+extern "C" void flash_attn_fwd_v3_doc_launch(
+    const void* q, const void* k, const void* v, void* out, void* lse, int B,
+    int H, int HKV, int S, float scale, const long long* strides,
+    const void* doc_start, hipStream_t stream) {
+  fwd_v3_launch<true>(q, k, v, out, lse, B, H, HKV, S, scale, strides,
+                      (const int*)doc_start, stream);
 }

@@ -62,6 +62,17 @@ void fa_bwd_dkv_v3_launch(const void*, const void*, const void*, const void*,
 void fa_bwd_dkv_launch(const void*, const void*, const void*, const void*,
                        const void*, const void*, void*, void*, int, int, int,
                        int, float, const long long*, void*);
+void flash_attn_fwd_v3_doc_launch(const void*, const void*, const void*, void*,
+                                  void*, int, int, int, int, float,
+                                  const long long*, const void*, void*);
+void fa_bwd_dq_v3_doc_launch(const void*, const void*, const void*,
+                             const void*, const void*, const void*, void*,
+                             int, int, int, int, float, const long long*,
+                             const void*, void*);
+void fa_bwd_dkv_v3_doc_launch(const void*, const void*, const void*,
+                              const void*, const void*, const void*, void*,
+                              void*, int, int, int, int, float,
+                              const long long*, const void*, void*);
 void f32_to_bf16_launch(const void*, void*, long long, void*);
 int mt_max_tensors();
 long long mt_auto_span(long long);
@@ -347,10 +358,52 @@ std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q,
   return {out, lse};
 }
 
-std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd(
+// document-mask arguments: int32 [B, S], contiguous, on q's device; the doc
+// variant exists for the v3 kernels only (D == 128, S % 256 == 0)
+static void check_doc_arg(const at::Tensor& d, const at::Tensor& q,
+                          const char* name) {
+  TORCH_CHECK(d.scalar_type() == at::kInt, name, " must be int32");
+  TORCH_CHECK(d.device() == q.device(), name, " must be on q's device");
+  TORCH_CHECK(d.dim() == 2 && d.size(0) == q.size(0) &&
+                  d.size(1) == q.size(2) && d.is_contiguous(),
+              name, " must be contiguous [B, S]");
+  TORCH_CHECK(q.size(3) == 128, "flash_attn_doc: head_dim must be 128");
+  TORCH_CHECK(q.size(2) % 256 == 0,
+              "flash_attn_doc: seq len must be a multiple of 256");
+}
+
+std::tuple<at::Tensor, at::Tensor> flash_attn_doc_fwd(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    double scale, const at::Tensor& doc_start) {
+  check_attn_view(q, "q");
+  check_attn_view(k, "k");
+  check_attn_view(v, "v");
+  check_doc_arg(doc_start, q, "doc_start");
+  const int B = (int)q.size(0), H = (int)q.size(1), S = (int)q.size(2);
+  const int D = (int)q.size(3), HKV = (int)k.size(1);
+  TORCH_CHECK(H % HKV == 0, "flash_attn: H % HKV != 0");
+  // same [B,S,H,D] output storage and stride staging as flash_attn_fwd
+  auto out_bshd = at::empty({B, S, H, D}, q.options());
+  auto out = out_bshd.permute({0, 2, 1, 3});
+  auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
+  long long st[12];
+  pack_strides(st, q, 0);
+  pack_strides(st, k, 3);
+  pack_strides(st, v, 6);
+  pack_strides(st, out, 9);
+  flash_attn_fwd_v3_doc_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                               out_bshd.data_ptr(), lse.data_ptr(), B, H, HKV,
+                               S, (float)scale, st, doc_start.data_ptr(),
+                               cur_stream());
+  return {out, lse};
+}
+
+// shared by flash_attn_bwd (doc_* null: the causal path, unchanged) and
+// flash_attn_doc_bwd
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd_impl(
     const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
     const at::Tensor& out, const at::Tensor& dout_in, const at::Tensor& lse,
-    double scale) {
+    double scale, const at::Tensor* doc_start, const at::Tensor* doc_end) {
   check_attn_view(q, "q");
   check_attn_view(k, "k");
   check_attn_view(v, "v");
@@ -405,7 +458,18 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd(
       }();
       auto dk32 = at::zeros({B, HKV, S, D}, k.options().dtype(at::kFloat));
       auto dv32 = at::zeros({B, HKV, S, D}, v.options().dtype(at::kFloat));
-      if (bwd_v3 && S % 256 == 0) {
+      if (doc_start != nullptr) {
+        fa_bwd_dq_v3_doc_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                dout.data_ptr(), lse.data_ptr(),
+                                dvec.data_ptr(), dq_bshd.data_ptr(), B, H,
+                                HKV, S, (float)scale, stq,
+                                doc_start->data_ptr(), cur_stream());
+        fa_bwd_dkv_v3_doc_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                 dout.data_ptr(), lse.data_ptr(),
+                                 dvec.data_ptr(), dk32.data_ptr(),
+                                 dv32.data_ptr(), B, H, HKV, S, (float)scale,
+                                 stq, doc_end->data_ptr(), cur_stream());
+      } else if (bwd_v3 && S % 256 == 0) {
         fa_bwd_dq_v3_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
                             dout.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
                             dq_bshd.data_ptr(), B, H, HKV, S, (float)scale,
@@ -434,6 +498,25 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd(
       return {dq, dk, dv};
     }
   }
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    const at::Tensor& out, const at::Tensor& dout, const at::Tensor& lse,
+    double scale) {
+  return flash_attn_bwd_impl(q, k, v, out, dout, lse, scale, nullptr,
+                             nullptr);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_doc_bwd(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    const at::Tensor& out, const at::Tensor& dout, const at::Tensor& lse,
+    double scale, const at::Tensor& doc_start, const at::Tensor& doc_end) {
+  check_attn_view(q, "q");
+  check_doc_arg(doc_start, q, "doc_start");
+  check_doc_arg(doc_end, q, "doc_end");
+  return flash_attn_bwd_impl(q, k, v, out, dout, lse, scale, &doc_start,
+                             &doc_end);
 }
 
 at::Tensor mfma16_probe(const at::Tensor& A, const at::Tensor& B) {
@@ -824,6 +907,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flash attention forward (bf16, causal, GQA, D=128) -> (out, lse)");
   m.def("flash_attn_bwd", &flash_attn_bwd,
         "flash attention backward -> (dq, dk, dv)");
+  m.def("flash_attn_doc_fwd", &flash_attn_doc_fwd,
+        "document-masked flash attention forward: query i sees key j iff "
+        "doc_start[b,i] <= j <= i (int32 [B,S]; D=128, S%256==0) -> (out, lse)");
+  m.def("flash_attn_doc_bwd", &flash_attn_doc_bwd,
+        "document-masked flash attention backward (doc_end[b,j] = exclusive "
+        "end of j's document) -> (dq, dk, dv)");
   m.attr("MT_MAX_TENSORS") = mt_max_tensors();
   m.def("multi_tensor_num_partials", &multi_tensor_num_partials,
         "partial slots multi_tensor_sq_norm needs for a tensor list",

@@ -41,6 +41,11 @@ def main():
                         "the fused optimizer (0 = off)")
     p.add_argument("--act-ckpt", action="store_true",
                    help="recompute transformer blocks in backward")
+    p.add_argument("--doc-len", type=int, default=0,
+                   help="pack every synthetic sequence from documents of this "
+                        "many tokens: attention and RoPE positions stay "
+                        "inside a document, the label of each document's "
+                        "last token is ignored (0 = one document)")
     args = p.parse_args()
 
     from dlrover_amd.models import LlamaConfig, LlamaForCausalLM
@@ -107,10 +112,21 @@ def main():
     ids = torch.randint(0, cfg.vocab_size, (args.batch, args.seq), device=device)
     labels = torch.randint(0, cfg.vocab_size, (args.batch, args.seq), device=device)
 
+    doc_start = None
+    if args.doc_len > 0:
+        from dlrover_amd.ops import doc_start_from_ids
+
+        idx = torch.arange(args.seq, device=device)
+        doc_start = doc_start_from_ids(
+            (idx // args.doc_len).expand(args.batch, args.seq))
+        # a document's last token has no next token of its own to predict
+        last = (idx % args.doc_len == args.doc_len - 1) | (idx == args.seq - 1)
+        labels[:, last] = -100
+
     for step in range(start_step + 1, args.steps + 1):
         t0 = time.perf_counter()
         with trainer.step():
-            loss = model(ids, labels)
+            loss = model(ids, labels, doc_start=doc_start)
             loss.backward()
         opt.step()
         opt.zero_grad()
