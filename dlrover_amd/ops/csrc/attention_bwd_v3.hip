@@ -24,69 +24,12 @@
 //
 // Fragment layouts + tr_b16 gather semantics: probe-verified
 // (tests/test_mfma_gpu.py, profiles/r02a_fa_v3.txt).
-#include <cstdlib>
-#include "kern_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+#include "attention_frag.h"
+#include "attention_launch.h"
 
 #define FB_D 128
 #define FB_QB 256  // q rows per dq block / kv rows per dkv block
 #define FB_T 64    // staged tile rows
-
-__device__ __forceinline__ int swzb(int row, int byte_col) {
-  return byte_col ^ ((row & 7) << 4);
-}
-
-__device__ __forceinline__ unsigned pk_bf16(float lo, float hi) {
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return *reinterpret_cast<unsigned*>(&v);
-}
-
-// cooperative-transpose A-fragment: X^T[d=n*32+(l&31)][rb+half*8 .. +8] from
-// a row-major swizzled [rows][128] LDS tile (see attention_v3.hip)
-__device__ __forceinline__ bf16x8 trT_frag(const char* lds, int rb, int n,
-                                           int lane, int half) {
-  const int j = (lane & 15) >> 2;
-  const int dq = n * 8 + ((lane & 16) >> 2) + (lane & 3);
-  const int r0 = rb + half * 8 + j;
-  const int r1 = r0 + 4;
-  const unsigned base = (unsigned)(uintptr_t)lds;
-  const unsigned a0 = base + r0 * 256 + ((dq * 8) ^ ((r0 & 7) << 4));
-  const unsigned a1 = base + r1 * 256 + ((dq * 8) ^ ((r1 & 7) << 4));
-  u32x2_t w0, w1;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %2\n\t"
-      "ds_read_b64_tr_b16 %1, %3\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=v"(w0), "=v"(w1)
-      : "v"(a0), "v"(a1));
-  u32x4_t frag = u32x4_t{w0.x, w0.y, w1.x, w1.y};
-  return *reinterpret_cast<bf16x8*>(&frag);
-}
-
-// B-operand fragments [16 rows, 32 cols] assembled from C-form per-lane
-// values v16 (16 f32, C rows (r&3)+8*(r>>2)+4*half, col = lane-own): two
-// k-slices of 16 rows each. See attention_v3.hip P^T derivation.
-__device__ __forceinline__ void pairswap_frags(const float v16[16], int half,
-                                               bf16x8 out[2]) {
-#pragma unroll
-  for (int ks2 = 0; ks2 < 2; ++ks2) {
-    const int r0 = ks2 * 8;
-    unsigned w0 = pk_bf16(v16[r0 + 0], v16[r0 + 1]);
-    unsigned w1 = pk_bf16(v16[r0 + 2], v16[r0 + 3]);
-    unsigned w2 = pk_bf16(v16[r0 + 4], v16[r0 + 5]);
-    unsigned w3 = pk_bf16(v16[r0 + 6], v16[r0 + 7]);
-    u32x2_t s0 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
-    u32x2_t s1 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
-    u32x4_t frag = u32x4_t{s0.x, s1.x, s0.y, s1.y};
-    out[ks2] = *reinterpret_cast<bf16x8*>(&frag);
-  }
-  (void)half;  // order is half-independent (see fwd derivation)
-}
 
 // ---------------------------------------------------------------------------
 // dQ kernel
@@ -171,9 +114,9 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
     for (int c = 0; c < 2; ++c) {
       const int col = st_col0 + c * 8;
       *reinterpret_cast<bf16x8*>(k_lds[buf] + st_row0 * 256 +
-                                 swzb(st_row0, col * 2)) = st_k[c];
+                                 swz(st_row0, col * 2)) = st_k[c];
       *reinterpret_cast<bf16x8*>(v_lds[buf] + st_row0 * 256 +
-                                 swzb(st_row0, col * 2)) = st_v[c];
+                                 swz(st_row0, col * 2)) = st_v[c];
     }
   };
 
@@ -216,7 +159,7 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
         for (int ks = 0; ks < 8; ++ks) {
           const int row = n * 32 + qcol;
           bf16x8 ak = *reinterpret_cast<const bf16x8*>(
-              k_cur + row * 256 + swzb(row, (ks * 16 + half * 8) * 2));
+              k_cur + row * 256 + swz(row, (ks * 16 + half * 8) * 2));
           acc_s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ak, bq[ks], acc_s,
                                                           0, 0, 0);
         }
@@ -236,7 +179,7 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
         for (int ks = 0; ks < 8; ++ks) {
           const int row = n * 32 + qcol;
           bf16x8 av = *reinterpret_cast<const bf16x8*>(
-              v_cur + row * 256 + swzb(row, (ks * 16 + half * 8) * 2));
+              v_cur + row * 256 + swz(row, (ks * 16 + half * 8) * 2));
           acc_dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bdo[ks],
                                                            acc_dp, 0, 0, 0);
         }
@@ -245,14 +188,14 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           dsv[r] = acc_s[r] * (acc_dp[r] - Dv) * scale;
-        pairswap_frags(dsv, half, &bds[n * 2]);
+        pairswap_frags(dsv, &bds[n * 2]);
       }
       // ---- dQ^T += K^T dS^T ----
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-          bf16x8 akT = trT_frag(k_cur, ks * 16, n, lane, half);
+          bf16x8 akT = tr_colT_frag(k_cur, ks * 16, n, lane, half);
           acc_dq[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               akT, bds[ks], acc_dq[n], 0, 0, 0);
         }
@@ -280,7 +223,7 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int d = n * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          *reinterpret_cast<__bf16*>(slab + qcol * 256 + swzb(qcol, d * 2)) =
+          *reinterpret_cast<__bf16*>(slab + qcol * 256 + swz(qcol, d * 2)) =
               (__bf16)acc_dq[n][r];
         }
       }
@@ -293,9 +236,9 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
         const int r2 = elem0 / FB_D;
         const int c2 = elem0 % FB_D;
         bf16x8 v0 = *reinterpret_cast<const bf16x8*>(
-            slab + r2 * 256 + swzb(r2, c2 * 2));
+            slab + r2 * 256 + swz(r2, c2 * 2));
         bf16x8 v1 = *reinterpret_cast<const bf16x8*>(
-            slab + r2 * 256 + swzb(r2, (c2 + 8) * 2));
+            slab + r2 * 256 + swz(r2, (c2 + 8) * 2));
         short* dst = dq_blk + (long long)(wave * 32 + r2) * qs_s + c2;
         *reinterpret_cast<bf16x8*>(dst) = v0;
         *reinterpret_cast<bf16x8*>(dst + 8) = v1;
@@ -360,10 +303,10 @@ __global__ __launch_bounds__(512) void fa_bwd_dq_v3_kernel(
       const int linear = (tid * 16) + c * 8;                                 \
       const int row = linear / FB_D;                                         \
       const int col = linear % FB_D;                                         \
-      *reinterpret_cast<bf16x8*>(q_lds + row * 256 + swzb(row, col * 2)) =   \
+      *reinterpret_cast<bf16x8*>(q_lds + row * 256 + swz(row, col * 2)) =   \
           *reinterpret_cast<const bf16x8*>(qsrc + (long long)row * qs_s +    \
                                            col);                             \
-      *reinterpret_cast<bf16x8*>(do_lds + row * 256 + swzb(row, col * 2)) =  \
+      *reinterpret_cast<bf16x8*>(do_lds + row * 256 + swz(row, col * 2)) =  \
           *reinterpret_cast<const bf16x8*>(dsrc + (long long)row * ds_s +    \
                                            col);                             \
     }                                                                        \
@@ -418,9 +361,7 @@ __global__ __launch_bounds__(512) void fa_bwd_dv_v3_kernel(
         for (int ks = 0; ks < 8; ++ks) {
           const int row = st * 32 + kcol;  // q row index == lane&31 pattern
           bf16x8 aq = *reinterpret_cast<const bf16x8*>(
-              q_lds + (st * 32 + kcol) * 256 +
-              swzb(st * 32 + kcol, (ks * 16 + half * 8) * 2));
-          (void)row;
+              q_lds + row * 256 + swz(row, (ks * 16 + half * 8) * 2));
           acc_s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq, bk[ks], acc_s,
                                                           0, 0, 0);
         }
@@ -437,14 +378,14 @@ __global__ __launch_bounds__(512) void fa_bwd_dv_v3_kernel(
                       : __expf(acc_s[r] * scale - l_lds[qrow]);
         }
         bf16x8 bp[2];
-        pairswap_frags(pv, half, bp);
+        pairswap_frags(pv, bp);
         // dV^T += dO^T P
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
 #pragma unroll
           for (int ks2 = 0; ks2 < 2; ++ks2) {
             bf16x8 adoT =
-                trT_frag(do_lds, st * 32 + ks2 * 16, n, lane, half);
+                tr_colT_frag(do_lds, st * 32 + ks2 * 16, n, lane, half);
             acc_dv[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
                 adoT, bp[ks2], acc_dv[n], 0, 0, 0);
           }
@@ -518,11 +459,11 @@ __global__ __launch_bounds__(512) void fa_bwd_dk_v3_kernel(
           const int row = st * 32 + kcol;
           const int bc = (ks * 16 + half * 8) * 2;
           bf16x8 aq = *reinterpret_cast<const bf16x8*>(
-              q_lds + row * 256 + swzb(row, bc));
+              q_lds + row * 256 + swz(row, bc));
           acc_s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq, bk[ks], acc_s,
                                                           0, 0, 0);
           bf16x8 ado = *reinterpret_cast<const bf16x8*>(
-              do_lds + row * 256 + swzb(row, bc));
+              do_lds + row * 256 + swz(row, bc));
           acc_dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ado, bv[ks],
                                                            acc_dp, 0, 0, 0);
         }
@@ -540,13 +481,14 @@ __global__ __launch_bounds__(512) void fa_bwd_dk_v3_kernel(
           dsv[r] = p * (acc_dp[r] - d_lds[qrow]) * scale;
         }
         bf16x8 bds[2];
-        pairswap_frags(dsv, half, bds);
+        pairswap_frags(dsv, bds);
         // dK^T += Q^T dS
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
 #pragma unroll
           for (int ks2 = 0; ks2 < 2; ++ks2) {
-            bf16x8 aqT = trT_frag(q_lds, st * 32 + ks2 * 16, n, lane, half);
+            bf16x8 aqT =
+                tr_colT_frag(q_lds, st * 32 + ks2 * 16, n, lane, half);
             acc_dk[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
                 aqT, bds[ks2], acc_dk[n], 0, 0, 0);
           }
@@ -595,19 +537,30 @@ extern "C" void fa_bwd_dkv_v3_launch(const void* q, const void* k,
                                      void* dk32, void* dv32, int B, int H,
                                      int HKV, int S, float scale,
                                      const long long* strides,
-                                     hipStream_t stream) {
-  dkv_v3_launch<false>(q, k, v, dout, lse, dvec, dk32, dv32, B, H, HKV, S,
-                       scale, strides, nullptr, stream);
+                                     const int* doc_end, hipStream_t stream) {
+  if (doc_end != nullptr)
+    dkv_v3_launch<true>(q, k, v, dout, lse, dvec, dk32, dv32, B, H, HKV, S,
+                        scale, strides, doc_end, stream);
+  else
+    dkv_v3_launch<false>(q, k, v, dout, lse, dvec, dk32, dv32, B, H, HKV, S,
+                         scale, strides, nullptr, stream);
 }
 
-// document-masked variant: doc_end is int32 [B, S], contiguous
-extern "C" void fa_bwd_dkv_v3_doc_launch(
-    const void* q, const void* k, const void* v, const void* dout,
-    const void* lse, const void* dvec, void* dk32, void* dv32, int B, int H,
-    int HKV, int S, float scale, const long long* strides,
-    const void* doc_end, hipStream_t stream) {
-  dkv_v3_launch<true>(q, k, v, dout, lse, dvec, dk32, dv32, B, H, HKV, S,
-                      scale, strides, (const int*)doc_end, stream);
+template <bool DOC>
+static void dq_v3_launch(const void* q, const void* k, const void* v,
+                         const void* dout, const void* lse, const void* dvec,
+                         void* dq, int B, int H, int HKV, int S, float scale,
+                         const long long* strides, const int* doc_start,
+                         hipStream_t stream) {
+  dim3 grid(S / FB_QB, H, B);
+  hipLaunchKernelGGL(fa_bwd_dq_v3_kernel<DOC>, grid, dim3(512), 0, stream,
+                     (const short*)q, (const short*)k, (const short*)v,
+                     (const short*)dout, (const float*)lse,
+                     (const float*)dvec, (short*)dq, B, H, HKV, S, scale,
+                     strides[0], strides[1], strides[2], strides[3],
+                     strides[4], strides[5], strides[6], strides[7],
+                     strides[8], strides[9], strides[10], strides[11],
+                     doc_start);
 }
 
 extern "C" void fa_bwd_dq_v3_launch(const void* q, const void* k,
@@ -615,31 +568,12 @@ extern "C" void fa_bwd_dq_v3_launch(const void* q, const void* k,
                                     const void* lse, const void* dvec,
                                     void* dq, int B, int H, int HKV, int S,
                                     float scale, const long long* strides,
+                                    const int* doc_start,
                                     hipStream_t stream) {
-  dim3 grid(S / FB_QB, H, B);
-  hipLaunchKernelGGL(fa_bwd_dq_v3_kernel<false>, grid, dim3(512), 0, stream,
-                     (const short*)q, (const short*)k, (const short*)v,
-                     (const short*)dout, (const float*)lse,
-                     (const float*)dvec, (short*)dq, B, H, HKV, S, scale,
-                     strides[0], strides[1], strides[2], strides[3],
-                     strides[4], strides[5], strides[6], strides[7],
-                     strides[8], strides[9], strides[10], strides[11],
-                     nullptr);
-}
-
-// document-masked variant: doc_start is int32 [B, S], contiguous
-extern "C" void fa_bwd_dq_v3_doc_launch(
-    const void* q, const void* k, const void* v, const void* dout,
-    const void* lse, const void* dvec, void* dq, int B, int H, int HKV, int S,
-    float scale, const long long* strides, const void* doc_start,
-    hipStream_t stream) {
-  dim3 grid(S / FB_QB, H, B);
-  hipLaunchKernelGGL(fa_bwd_dq_v3_kernel<true>, grid, dim3(512), 0, stream,
-                     (const short*)q, (const short*)k, (const short*)v,
-                     (const short*)dout, (const float*)lse,
-                     (const float*)dvec, (short*)dq, B, H, HKV, S, scale,
-                     strides[0], strides[1], strides[2], strides[3],
-                     strides[4], strides[5], strides[6], strides[7],
-                     strides[8], strides[9], strides[10], strides[11],
-                     (const int*)doc_start);
+  if (doc_start != nullptr)
+    dq_v3_launch<true>(q, k, v, dout, lse, dvec, dq, B, H, HKV, S, scale,
+                       strides, doc_start, stream);
+  else
+    dq_v3_launch<false>(q, k, v, dout, lse, dvec, dq, B, H, HKV, S, scale,
+                        strides, nullptr, stream);
 }

@@ -14,76 +14,27 @@
 //   softmax row state (m, l) is then ONE scalar per lane — no cross-lane
 //   reduction beyond a single permlane32_swap exchange with the partner.
 //
-//   PV SWAPPED TOO: O^T = V^T @ P^T with A = V^T [32 d x 16 kv] (b128 reads
-//   from the swizzled V^T LDS), B = P^T [16 kv x 32 q] — the B fragment is
-//   assembled IN REGISTERS from the QK^T output via bf16 packing plus ONE
-//   permlane32_swap per register pair (T12). O accumulator: col = q again,
-//   so the online-softmax alpha rescale is a per-lane SCALAR multiply.
+//   PV SWAPPED TOO: O^T = V^T @ P^T with A = V^T [32 d x 16 kv] (gathered
+//   from the row-major V tile with ds_read_b64_tr_b16, tr_colT_frag),
+//   B = P^T [16 kv x 32 q] — the B fragment is assembled IN REGISTERS from
+//   the QK^T output via bf16 packing plus ONE permlane32_swap per register
+//   pair (T12, pairswap_frags). O accumulator: col = q again, so the
+//   online-softmax alpha rescale is a per-lane SCALAR multiply.
 //
-//   LDS: K[64][128] + V^T[128][64], XOR-swizzled, x2 buffers = 64 KB; no P
-//   buffer. T14 async-stage: next tile's global loads issue before compute,
-//   LDS writes land after the barrier.
+//   LDS: K[64][128] + V[64][128], both row-major and XOR-swizzled, x2
+//   buffers = 64 KB; no P buffer. T14 async-stage: next tile's global loads
+//   issue before compute, LDS writes land after the barrier.
 //
 // The reference (DLRover) has no attention kernel of its own — this is the
 // MI355X-native hot path (BASELINE.json north star).
-#include <cstdlib>
-#include "kern_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+#include "attention_frag.h"
+#include "attention_launch.h"
 
 #define FA3_D 128
 #define FA3_QB 256  // q rows per block
 #define FA3_QW 32   // q rows per wave
 #define FA3_KT 64   // kv rows per tile
 
-// XOR swizzle on a byte offset within a 256 B LDS row (guide G4)
-__device__ __forceinline__ int swz3(int row, int byte_col) {
-  return byte_col ^ ((row & 7) << 4);
-}
-
-// pack two fp32 into one u32 of two bf16 (compiler emits v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return *reinterpret_cast<unsigned*>(&v);
-}
-
-// A-operand fragment X^T[d = n*32 + (l&31)][row = rb + half*8 + i] read from
-// a ROW-major swz3-swizzled [rows][128] bf16 LDS tile via two cooperative
-// ds_read_b64_tr_b16 gathers. Semantics probe-pinned (profiles/r02a): the
-// 16-lane group's addresses form a gather table — lane l supplies the word
-// address for (row rb + ((l&15)>>2), d-quad base+(l&3)) and receives, as
-// element j, its OWN d column of row rb + j (slots 4j + ((l>>2)&3)).
-__device__ __forceinline__ bf16x8 tr_colT_frag(const char* lds, int rb,
-                                               int n, int lane, int half) {
-  typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_;
-  const int j = (lane & 15) >> 2;
-  const int dq = n * 8 + ((lane & 16) >> 2) + (lane & 3);
-  const int r0 = rb + half * 8 + j;
-  const int r1 = r0 + 4;
-  const unsigned base = (unsigned)(uintptr_t)lds;
-  const unsigned a0 = base + r0 * 256 + ((dq * 8) ^ ((r0 & 7) << 4));
-  const unsigned a1 = base + r1 * 256 + ((dq * 8) ^ ((r1 & 7) << 4));
-  u32x2_ w0, w1;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %2\n\t"
-      "ds_read_b64_tr_b16 %1, %3\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=v"(w0), "=v"(w1)
-      : "v"(a0), "v"(a1));
-  u32x4_t frag = u32x4_t{w0.x, w0.y, w1.x, w1.y};
-  return *reinterpret_cast<bf16x8*>(&frag);
-}
-
-// TRV=false: V staged TRANSPOSED (vt_lds, per-element scatter writes — the
-//   measured bank-conflict source) and PV A-operand read b128.
-// TRV=true ("v4"): V staged ROW-major like K (conflict-free b128 writes) and
-//   the V^T A-operand gathered with ds_read_b64_tr_b16 (tr_colT_frag).
-//
 // DOC=true ("document mask", packed sequences): query i attends key j iff
 //   doc_start[b][i] <= j <= i. Same MFMA sequence, LDS layout and staging; the
 //   variant is one more comparison per score against a per-lane scalar, a
@@ -91,7 +42,7 @@ __device__ __forceinline__ bf16x8 tr_colT_frag(const char* lds, int rb,
 //   the wave's first document. Everything read from doc_start is clamped, so
 //   arbitrary int32 content can give wrong numbers but never a bad address.
 //   DOC=false is the causal kernel: doc_start is never read.
-template <bool TRV, bool DOC>
+template <bool DOC>
 __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, short* __restrict__ out,
@@ -101,8 +52,8 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
     long long vs_b, long long vs_h, long long vs_s,
     long long os_b, long long os_h, long long os_s,
     const int* __restrict__ doc_start) {
-  __shared__ char k_lds[2][FA3_KT * FA3_D * 2];   // 2 x 16 KB
-  __shared__ char vt_lds[2][FA3_D * FA3_KT * 2];  // 2 x 16 KB
+  __shared__ char k_lds[2][FA3_KT * FA3_D * 2];  // 2 x 16 KB, row-major swz
+  __shared__ char v_lds[2][FA3_KT * FA3_D * 2];  // 2 x 16 KB, row-major swz
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -161,26 +112,17 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
 
   auto write_lds = [&](int buf) {
     char* kb = k_lds[buf];
-    char* vb = vt_lds[buf];
+    char* vb = v_lds[buf];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       const int col = st_col0 + c * 8;
-      *reinterpret_cast<bf16x8*>(kb + st_row0 * 256 + swz3(st_row0, col * 2)) =
+      *reinterpret_cast<bf16x8*>(kb + st_row0 * 256 + swz(st_row0, col * 2)) =
           st_k[c];
-      if (TRV) {
-        // row-major like K: conflict-free b128 store; the transpose happens
-        // on READ via the tr_b16 cooperative gather
-        *reinterpret_cast<bf16x8*>(vb + st_row0 * 256 +
-                                   swz3(st_row0, col * 2)) = st_v[c];
-      } else {
-        // V transposed: element (row, col+i) -> vt[col+i][row]
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int trow = col + i;
-          *reinterpret_cast<__bf16*>(vb + trow * 128 +
-                                     swz3(trow, st_row0 * 2)) = st_v[c][i];
-        }
-      }
+      // V row-major like K: conflict-free b128 store (a transposed V tile
+      // needs per-element scatter writes, the measured bank-conflict
+      // source); the transpose happens on READ via the tr_b16 gather
+      *reinterpret_cast<bf16x8*>(vb + st_row0 * 256 + swz(st_row0, col * 2)) =
+          st_v[c];
     }
   };
 
@@ -209,7 +151,7 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
   for (int kt = kt0; kt < n_tiles; ++kt) {
     const int cur = (kt - kt0) & 1;  // tile kt0 sits in buffer 0
     const char* k_cur = k_lds[cur];
-    const char* vt_cur = vt_lds[cur];
+    const char* v_cur = v_lds[cur];
     if (kt + 1 < n_tiles) issue_loads(kt + 1);  // T14: issue early
 
     const int kv0 = kt * FA3_KT;
@@ -235,7 +177,7 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
             const int row = n * 32 + qcol;
             const int byte_col = (ks * 16 + half * 8) * 2;
             ak = *reinterpret_cast<const bf16x8*>(
-                k_cur + row * 256 + swz3(row, byte_col));
+                k_cur + row * 256 + swz(row, byte_col));
           }
           acc_s[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ak, bq[ks],
                                                              acc_s[n], 0, 0, 0);
@@ -298,35 +240,10 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc_o[n][r] *= alpha;
 
-      // ---- assemble P^T B-frags: pack pairs to bf16, ONE swap per pair ---
-      // own regs r, r+1 = kv (base + 0,1); partner holds (base + 4,5).
-      // After permlane32_swap(a=own pair, b=own pair+4):
-      //   half 0 lanes: a' = kv(+0,1), b' = partner kv(+4,5)
-      //   half 1 lanes: a' = partner's,  b (own) = kv(+12,13) ...
-      // yielding for every lane the 8 kv slots (half*8 .. half*8+8) of each
-      // 16-kv k-slice, i.e. exactly the B fragment.
+      // ---- assemble P^T B-frags in registers (no LDS round trip) ----
       bf16x8 bp[4];  // k-slices: [subtile n][ks within 32] = n*2 + ks
-#pragma unroll
-      for (int n = 0; n < 2; ++n) {
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2) {
-          // k-slice covers kv = n*32 + ks2*16 + [0,16)
-          // own regs for this slice: r0 = ks2*8 (kv base n*32+ks2*16+4*half)
-          const int r0 = n * 16 + ks2 * 8;
-          unsigned w0 = pack_bf16(p[r0 + 0], p[r0 + 1]);
-          unsigned w1 = pack_bf16(p[r0 + 2], p[r0 + 3]);
-          unsigned w2 = pack_bf16(p[r0 + 4], p[r0 + 5]);
-          unsigned w3 = pack_bf16(p[r0 + 6], p[r0 + 7]);
-          // swap(vdst, vsrc) exchanges vdst's lanes 32-63 with vsrc's 0-31:
-          //   .x (new w0): h0 lanes own kv(+0,1); h1 lanes partner kv(+8,9)
-          //   .y (new w2): h0 lanes partner kv(+4,5); h1 lanes own kv(+12,13)
-          // -> frag order [x0, x1, y0, y1] is the SAME for both halves
-          u32x2_t s0 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
-          u32x2_t s1 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
-          u32x4_t frag = u32x4_t{s0.x, s1.x, s0.y, s1.y};
-          bp[n * 2 + ks2] = *reinterpret_cast<bf16x8*>(&frag);
-        }
-      }
+      pairswap_frags(&p[0], &bp[0]);
+      pairswap_frags(&p[16], &bp[2]);
 
       // ---- O^T += V^T @ P^T ----
 #pragma unroll
@@ -334,15 +251,7 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {  // kv k-slices of 16
           // A = V^T[d = n*32 + (lane&31)][kv = ks*16 + half*8 + i]
-          bf16x8 av;
-          if (TRV) {
-            av = tr_colT_frag(vt_cur, ks * 16, n, lane, half);
-          } else {
-            const int row = n * 32 + qcol;
-            const int byte_col = (ks * 16 + half * 8) * 2;
-            av = *reinterpret_cast<const bf16x8*>(
-                vt_cur + row * 128 + swz3(row, byte_col));
-          }
+          bf16x8 av = tr_colT_frag(v_cur, ks * 16, n, lane, half);
           acc_o[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bp[ks],
                                                              acc_o[n], 0, 0, 0);
         }
@@ -373,7 +282,7 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int d = n * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          *reinterpret_cast<__bf16*>(slab + qcol * 256 + swz3(qcol, d * 2)) =
+          *reinterpret_cast<__bf16*>(slab + qcol * 256 + swz(qcol, d * 2)) =
               (__bf16)(acc_o[n][r] * inv);
         }
       }
@@ -388,9 +297,9 @@ __global__ __launch_bounds__(512) void flash_attn_fwd_v3_kernel(
         const int r2 = elem0 / FA3_D;
         const int c2 = elem0 % FA3_D;
         bf16x8 v0 = *reinterpret_cast<const bf16x8*>(
-            slab + r2 * 256 + swz3(r2, c2 * 2));
+            slab + r2 * 256 + swz(r2, c2 * 2));
         bf16x8 v1 = *reinterpret_cast<const bf16x8*>(
-            slab + r2 * 256 + swz3(r2, (c2 + 8) * 2));
+            slab + r2 * 256 + swz(r2, (c2 + 8) * 2));
         short* dst = o_blk + (long long)(wave * FA3_QW + r2) * os_s + c2;
         *reinterpret_cast<bf16x8*>(dst) = v0;
         *reinterpret_cast<bf16x8*>(dst + 8) = v1;
@@ -409,44 +318,25 @@ static void fwd_v3_launch(const void* q, const void* k, const void* v,
                           float scale, const long long* strides,
                           const int* doc_start, hipStream_t stream) {
   dim3 grid(S / FA3_QB, H, B);
-  // v4 (tr-read V, conflict-free staging) unless DLROVER_FA_TRV=0
-  static const bool trv = []() {
-    const char* e = getenv("DLROVER_FA_TRV");
-    return e == nullptr || e[0] != '0';
-  }();
-  if (trv) {
-    hipLaunchKernelGGL((flash_attn_fwd_v3_kernel<true, DOC>), grid, dim3(512),
-                       0, stream, (const short*)q, (const short*)k,
-                       (const short*)v, (short*)out, (float*)lse, B, H, HKV,
-                       S, scale, strides[0], strides[1], strides[2],
-                       strides[3], strides[4], strides[5], strides[6],
-                       strides[7], strides[8], strides[9], strides[10],
-                       strides[11], doc_start);
-  } else {
-    hipLaunchKernelGGL((flash_attn_fwd_v3_kernel<false, DOC>), grid,
-                       dim3(512), 0, stream, (const short*)q, (const short*)k,
-                       (const short*)v, (short*)out, (float*)lse, B, H, HKV,
-                       S, scale, strides[0], strides[1], strides[2],
-                       strides[3], strides[4], strides[5], strides[6],
-                       strides[7], strides[8], strides[9], strides[10],
-                       strides[11], doc_start);
-  }
+  hipLaunchKernelGGL(flash_attn_fwd_v3_kernel<DOC>, grid, dim3(512), 0,
+                     stream, (const short*)q, (const short*)k,
+                     (const short*)v, (short*)out, (float*)lse, B, H, HKV, S,
+                     scale, strides[0], strides[1], strides[2], strides[3],
+                     strides[4], strides[5], strides[6], strides[7],
+                     strides[8], strides[9], strides[10], strides[11],
+                     doc_start);
 }
 
 extern "C" void flash_attn_fwd_v3_launch(const void* q, const void* k,
                                          const void* v, void* out, void* lse,
                                          int B, int H, int HKV, int S,
                                          float scale, const long long* strides,
+                                         const int* doc_start,
                                          hipStream_t stream) {
-  fwd_v3_launch<false>(q, k, v, out, lse, B, H, HKV, S, scale, strides,
-                       nullptr, stream);
-}
-
-// document-masked variant: doc_start is int32 [B, S], contiguous
-extern "C" void flash_attn_fwd_v3_doc_launch(
-    const void* q, const void* k, const void* v, void* out, void* lse, int B,
-    int H, int HKV, int S, float scale, const long long* strides,
-    const void* doc_start, hipStream_t stream) {
-  fwd_v3_launch<true>(q, k, v, out, lse, B, H, HKV, S, scale, strides,
-                      (const int*)doc_start, stream);
+  if (doc_start != nullptr)
+    fwd_v3_launch<true>(q, k, v, out, lse, B, H, HKV, S, scale, strides,
+                        doc_start, stream);
+  else
+    fwd_v3_launch<false>(q, k, v, out, lse, B, H, HKV, S, scale, strides,
+                         nullptr, stream);
 }

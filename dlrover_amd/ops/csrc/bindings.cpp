@@ -9,6 +9,8 @@
 #include <tuple>
 #include <vector>
 
+#include "attention_launch.h"
+
 extern "C" {
 void rmsnorm_fwd_launch(const void*, const void*, void*, void*, int, int,
                         float, void*);
@@ -39,41 +41,6 @@ void mfma16_probe_launch(const void*, const void*, void*, void*);
 void mfma32_probe_launch(const void*, const void*, void*, void*);
 void tr_b16_probe3_launch(void*, void*);
 void tr_b16_probe_launch(void*, void*);
-void flash_attn_fwd_launch(const void*, const void*, const void*, void*,
-                           void*, int, int, int, int, float,
-                           const long long*, void*);
-void flash_attn_fwd_v3_launch(const void*, const void*, const void*, void*,
-                              void*, int, int, int, int, float,
-                              const long long*, void*);
-void flash_attn_fwd_v2_launch(const void*, const void*, const void*, void*,
-                              void*, int, int, int, int, float,
-                              const long long*, void*);
-void fa_bwd_pre_launch(const void*, const void*, void*, int, int, int,
-                       const long long*, const long long*, void*);
-void fa_bwd_dq_launch(const void*, const void*, const void*, const void*,
-                      const void*, const void*, void*, int, int, int, int,
-                      float, const long long*, void*);
-void fa_bwd_dq_v3_launch(const void*, const void*, const void*, const void*,
-                         const void*, const void*, void*, int, int, int, int,
-                         float, const long long*, void*);
-void fa_bwd_dkv_v3_launch(const void*, const void*, const void*, const void*,
-                          const void*, const void*, void*, void*, int, int,
-                          int, int, float, const long long*, void*);
-void fa_bwd_dkv_launch(const void*, const void*, const void*, const void*,
-                       const void*, const void*, void*, void*, int, int, int,
-                       int, float, const long long*, void*);
-void flash_attn_fwd_v3_doc_launch(const void*, const void*, const void*, void*,
-                                  void*, int, int, int, int, float,
-                                  const long long*, const void*, void*);
-void fa_bwd_dq_v3_doc_launch(const void*, const void*, const void*,
-                             const void*, const void*, const void*, void*,
-                             int, int, int, int, float, const long long*,
-                             const void*, void*);
-void fa_bwd_dkv_v3_doc_launch(const void*, const void*, const void*,
-                              const void*, const void*, const void*, void*,
-                              void*, int, int, int, int, float,
-                              const long long*, const void*, void*);
-void f32_to_bf16_launch(const void*, void*, long long, void*);
 int mt_max_tensors();
 long long mt_auto_span(long long);
 long long mt_num_blocks(int, const long long*, long long);
@@ -289,215 +256,204 @@ void causal_softmax_bwd(at::Tensor& dscores, const at::Tensor& probs,
                             row_len, (float)scale, cur_stream());
 }
 
+// ---- flash attention ------------------------------------------------------
 // q/k/v/out are LOGICALLY [B,H,S,D]; strided permuted views are fine as long
 // as the last (D) dim is contiguous — no transpose copies needed.
-static void check_attn_view(const at::Tensor& t, const char* name) {
+void check_attn_view(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, name,
               " must be bf16 GPU");
   TORCH_CHECK(t.dim() == 4 && t.stride(3) == 1, name,
               " must be [B,H,S,D] with contiguous D");
 }
 
-static void pack_strides(long long* st, const at::Tensor& t, int at) {
+void pack_strides(long long* st, const at::Tensor& t, int at) {
   st[at + 0] = (long long)t.stride(0);
   st[at + 1] = (long long)t.stride(1);
   st[at + 2] = (long long)t.stride(2);
+}
+
+hipStream_t attn_stream() {
+  return at::cuda::getCurrentCUDAStream().stream();
+}
+
+struct AttnShape {
+  int B, H, HKV, S, D;
+};
+
+// everything the kernels assume about q/k/v, forward and backward alike
+AttnShape check_attn_qkv(const at::Tensor& q, const at::Tensor& k,
+                         const at::Tensor& v) {
+  check_attn_view(q, "q");
+  check_attn_view(k, "k");
+  check_attn_view(v, "v");
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device(),
+              "flash_attn: q, k and v must be on one device");
+  TORCH_CHECK(k.sizes() == v.sizes(),
+              "flash_attn: k and v must have the same shape");
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) &&
+                  k.size(3) == q.size(3),
+              "flash_attn: k/v must have q's B, S and D");
+  const AttnShape s = {(int)q.size(0), (int)q.size(1), (int)k.size(1),
+                       (int)q.size(2), (int)q.size(3)};
+  TORCH_CHECK(s.D == 128, "flash_attn: head_dim must be 128");
+  TORCH_CHECK(s.S % 64 == 0, "flash_attn: seq len must be a multiple of 64");
+  TORCH_CHECK(s.HKV > 0 && s.H % s.HKV == 0, "flash_attn: H % HKV != 0");
+  return s;
+}
+
+// The 32x32-MFMA kernels (attention_v3.hip, attention_bwd_v3.hip) own 256-row
+// blocks; every other S (a multiple of 64) runs the 16x16 kernels. Forward
+// and backward use the same rule.
+bool attn_use_v3(int S) { return S % 256 == 0; }
+
+// document-mask arguments: int32 [B, S], contiguous, on q's device; only the
+// v3 kernels have the DOC variant
+void check_doc_arg(const at::Tensor& d, const at::Tensor& q,
+                   const char* name) {
+  TORCH_CHECK(d.scalar_type() == at::kInt, name, " must be int32");
+  TORCH_CHECK(d.device() == q.device(), name, " must be on q's device");
+  TORCH_CHECK(d.dim() == 2 && d.size(0) == q.size(0) &&
+                  d.size(1) == q.size(2) && d.is_contiguous(),
+              name, " must be contiguous [B, S]");
+  TORCH_CHECK(attn_use_v3((int)q.size(2)),
+              "flash_attn_doc: seq len must be a multiple of 256");
+}
+
+const int* doc_ptr(const at::Tensor* d) {
+  return d != nullptr ? (const int*)d->data_ptr() : nullptr;
+}
+
+// doc_start null: the causal path
+std::tuple<at::Tensor, at::Tensor> flash_attn_fwd_impl(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    double scale, const at::Tensor* doc_start) {
+  const AttnShape s = check_attn_qkv(q, k, v);
+  if (doc_start != nullptr) check_doc_arg(*doc_start, q, "doc_start");
+  // output in [B,S,H,D] storage (what the model consumes — avoids the
+  // transpose-back copy); returned as a [B,H,S,D] view
+  auto out_bshd = at::empty({s.B, s.S, s.H, s.D}, q.options());
+  auto out = out_bshd.permute({0, 2, 1, 3});
+  auto lse = at::empty({s.B, s.H, s.S}, q.options().dtype(at::kFloat));
+  long long st[12];
+  pack_strides(st, q, 0);
+  pack_strides(st, k, 3);
+  pack_strides(st, v, 6);
+  pack_strides(st, out, 9);
+  if (attn_use_v3(s.S)) {
+    flash_attn_fwd_v3_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                             out_bshd.data_ptr(), lse.data_ptr(), s.B, s.H,
+                             s.HKV, s.S, (float)scale, st, doc_ptr(doc_start),
+                             attn_stream());
+  } else {
+    flash_attn_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                          out_bshd.data_ptr(), lse.data_ptr(), s.B, s.H,
+                          s.HKV, s.S, (float)scale, st, attn_stream());
+  }
+  return {out, lse};
 }
 
 std::tuple<at::Tensor, at::Tensor> flash_attn_fwd(const at::Tensor& q,
                                                   const at::Tensor& k,
                                                   const at::Tensor& v,
                                                   double scale) {
-  check_attn_view(q, "q");
-  check_attn_view(k, "k");
-  check_attn_view(v, "v");
-  const int B = (int)q.size(0), H = (int)q.size(1), S = (int)q.size(2);
-  const int D = (int)q.size(3), HKV = (int)k.size(1);
-  TORCH_CHECK(D == 128, "flash_attn: head_dim must be 128");
-  TORCH_CHECK(S % 64 == 0, "flash_attn: seq len must be a multiple of 64");
-  TORCH_CHECK(H % HKV == 0, "flash_attn: H % HKV != 0");
-  // output in [B,S,H,D] storage (what the model consumes — avoids the
-  // transpose-back copy); returned as a [B,H,S,D] view
-  auto out_bshd = at::empty({B, S, H, D}, q.options());
-  auto out = out_bshd.permute({0, 2, 1, 3});
-  auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
-  long long st[12];
-  pack_strides(st, q, 0);
-  pack_strides(st, k, 3);
-  pack_strides(st, v, 6);
-  pack_strides(st, out, 9);
-  // DLROVER_FA_V2=1 selects the experimental ds_read_b64_tr_b16 PV path.
-  // Hardware measurement showed the tr read takes its tile-selecting
-  // address bits from the 16-lane GROUP LEADER (only bits 1-2 act
-  // per-lane), so the per-lane-tile v2 design reads wrong columns for
-  // sub>3 — kept off until the round-2 redesign (see attention.hip).
-  static const bool use_v2 = []() {
-    const char* e = getenv("DLROVER_FA_V2");
-    return e != nullptr && e[0] == '1';
-  }();
-  // V3 (default when shapes allow): 32x32x16 MFMA, swapped operands,
-  // in-register online softmax — attention_v3.hip. DLROVER_FA_V3=0 falls
-  // back to v1 (16x16x32 + LDS-staged P).
-  static const bool v3_enabled = []() {
-    const char* e = getenv("DLROVER_FA_V3");
-    return e == nullptr || e[0] != '0';
-  }();
-  if (v3_enabled && !use_v2 && S % 256 == 0) {
-    flash_attn_fwd_v3_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                             out_bshd.data_ptr(), lse.data_ptr(), B, H, HKV,
-                             S, (float)scale, st, cur_stream());
-  } else if (use_v2) {
-    flash_attn_fwd_v2_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                             out_bshd.data_ptr(), lse.data_ptr(), B, H, HKV,
-                             S, (float)scale, st, cur_stream());
-  } else {
-    flash_attn_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                          out_bshd.data_ptr(), lse.data_ptr(), B, H, HKV, S,
-                          (float)scale, st, cur_stream());
-  }
-  return {out, lse};
-}
-
-// document-mask arguments: int32 [B, S], contiguous, on q's device; the doc
-// variant exists for the v3 kernels only (D == 128, S % 256 == 0)
-static void check_doc_arg(const at::Tensor& d, const at::Tensor& q,
-                          const char* name) {
-  TORCH_CHECK(d.scalar_type() == at::kInt, name, " must be int32");
-  TORCH_CHECK(d.device() == q.device(), name, " must be on q's device");
-  TORCH_CHECK(d.dim() == 2 && d.size(0) == q.size(0) &&
-                  d.size(1) == q.size(2) && d.is_contiguous(),
-              name, " must be contiguous [B, S]");
-  TORCH_CHECK(q.size(3) == 128, "flash_attn_doc: head_dim must be 128");
-  TORCH_CHECK(q.size(2) % 256 == 0,
-              "flash_attn_doc: seq len must be a multiple of 256");
+  return flash_attn_fwd_impl(q, k, v, scale, nullptr);
 }
 
 std::tuple<at::Tensor, at::Tensor> flash_attn_doc_fwd(
     const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
     double scale, const at::Tensor& doc_start) {
-  check_attn_view(q, "q");
-  check_attn_view(k, "k");
-  check_attn_view(v, "v");
-  check_doc_arg(doc_start, q, "doc_start");
-  const int B = (int)q.size(0), H = (int)q.size(1), S = (int)q.size(2);
-  const int D = (int)q.size(3), HKV = (int)k.size(1);
-  TORCH_CHECK(H % HKV == 0, "flash_attn: H % HKV != 0");
-  // same [B,S,H,D] output storage and stride staging as flash_attn_fwd
-  auto out_bshd = at::empty({B, S, H, D}, q.options());
-  auto out = out_bshd.permute({0, 2, 1, 3});
-  auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
-  long long st[12];
-  pack_strides(st, q, 0);
-  pack_strides(st, k, 3);
-  pack_strides(st, v, 6);
-  pack_strides(st, out, 9);
-  flash_attn_fwd_v3_doc_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                               out_bshd.data_ptr(), lse.data_ptr(), B, H, HKV,
-                               S, (float)scale, st, doc_start.data_ptr(),
-                               cur_stream());
-  return {out, lse};
+  return flash_attn_fwd_impl(q, k, v, scale, &doc_start);
 }
 
-// shared by flash_attn_bwd (doc_* null: the causal path, unchanged) and
-// flash_attn_doc_bwd
-static std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd_impl(
+// out / dout: bf16 on q's device with q's logical shape
+void check_attn_like_q(const at::Tensor& t, const at::Tensor& q,
+                       const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == q.device() &&
+                  t.scalar_type() == at::kBFloat16,
+              name, " must be bf16 on q's device");
+  TORCH_CHECK(t.sizes() == q.sizes(), name, " must have q's shape");
+}
+
+// doc_start / doc_end both null: the causal path
+std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd_impl(
     const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
     const at::Tensor& out, const at::Tensor& dout_in, const at::Tensor& lse,
     double scale, const at::Tensor* doc_start, const at::Tensor* doc_end) {
-  check_attn_view(q, "q");
-  check_attn_view(k, "k");
-  check_attn_view(v, "v");
-  const int B = (int)q.size(0), H = (int)q.size(1), S = (int)q.size(2);
-  const int D = (int)q.size(3), HKV = (int)k.size(1);
+  const AttnShape s = check_attn_qkv(q, k, v);
+  check_attn_like_q(out, q, "out");
+  TORCH_CHECK(out.stride(3) == 1, "out needs contiguous D");
+  check_attn_like_q(dout_in, q, "dout");
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() &&
+                  lse.scalar_type() == at::kFloat,
+              "lse must be fp32 on q's device");
+  TORCH_CHECK(lse.is_contiguous() &&
+                  lse.sizes() == at::IntArrayRef({s.B, s.H, s.S}),
+              "lse must be contiguous [B, H, S]");
+  if (doc_start != nullptr) {
+    check_doc_arg(*doc_start, q, "doc_start");
+    check_doc_arg(*doc_end, q, "doc_end");
+  }
   // the preprocess + dkv stage read dO/O with [B,S,H,D]-style strides; accept
   // any incoming grad layout by normalizing dO into out's layout
   at::Tensor dout = dout_in;
   if (dout.strides() != out.strides()) {
-    dout = at::empty_like(out.permute({0, 2, 1, 3}).contiguous())
-               .view({B, S, H, D});
-    dout = dout.permute({0, 2, 1, 3});
+    dout = at::empty({s.B, s.S, s.H, s.D}, out.options())
+               .permute({0, 2, 1, 3});
     dout.copy_(dout_in);
   }
   TORCH_CHECK(dout.stride(3) == 1, "dout needs contiguous D");
-  auto dvec = at::empty({B, H, S}, q.options().dtype(at::kFloat));
-  {
-    long long ost[3], dstr[3];
-    pack_strides(ost, out, 0);
-    pack_strides(dstr, dout, 0);
-    fa_bwd_pre_launch(dout.data_ptr(), out.data_ptr(), dvec.data_ptr(), B, H,
-                      S, ost, dstr, cur_stream());
-    long long st[12];
-    pack_strides(st, q, 0);
-    pack_strides(st, k, 3);
-    pack_strides(st, v, 6);
-    pack_strides(st, dout, 9);
-    // dq mirrors q's layout: allocate [B,S,H,D] storage, return as view
-    auto dq_bshd = at::empty({B, S, H, D}, q.options());
-    auto dq = dq_bshd.permute({0, 2, 1, 3});
-    {
-      long long stq[12];
-      pack_strides(stq, dq, 0);
-      pack_strides(stq, k, 3);
-      pack_strides(stq, v, 6);
-      pack_strides(stq, dout, 9);
-      // q-strides slot is used for BOTH q loads and dq stores in the kernel;
-      // they must match, so stage q into dq's layout if they differ
-      at::Tensor quse = q;
-      if (q.strides() != dq.strides()) {
-        auto q_bshd = at::empty({B, S, H, D}, q.options());
-        auto qv = q_bshd.permute({0, 2, 1, 3});
-        qv.copy_(q);
-        quse = qv;
-        pack_strides(stq, quse, 0);
-      }
-      // v3 backward (32x32 MFMA swapped rebuild) when shapes allow;
-      // DLROVER_FA_BWD_V3=0 reverts to the 16x16 kernels
-      static const bool bwd_v3 = []() {
-        const char* e = getenv("DLROVER_FA_BWD_V3");
-        return e == nullptr || e[0] != '0';
-      }();
-      auto dk32 = at::zeros({B, HKV, S, D}, k.options().dtype(at::kFloat));
-      auto dv32 = at::zeros({B, HKV, S, D}, v.options().dtype(at::kFloat));
-      if (doc_start != nullptr) {
-        fa_bwd_dq_v3_doc_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                dout.data_ptr(), lse.data_ptr(),
-                                dvec.data_ptr(), dq_bshd.data_ptr(), B, H,
-                                HKV, S, (float)scale, stq,
-                                doc_start->data_ptr(), cur_stream());
-        fa_bwd_dkv_v3_doc_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                 dout.data_ptr(), lse.data_ptr(),
-                                 dvec.data_ptr(), dk32.data_ptr(),
-                                 dv32.data_ptr(), B, H, HKV, S, (float)scale,
-                                 stq, doc_end->data_ptr(), cur_stream());
-      } else if (bwd_v3 && S % 256 == 0) {
-        fa_bwd_dq_v3_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
-                            dout.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
-                            dq_bshd.data_ptr(), B, H, HKV, S, (float)scale,
-                            stq, cur_stream());
-        fa_bwd_dkv_v3_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
-                             dout.data_ptr(), lse.data_ptr(),
-                             dvec.data_ptr(), dk32.data_ptr(),
-                             dv32.data_ptr(), B, H, HKV, S, (float)scale,
-                             stq, cur_stream());
-      } else {
-        fa_bwd_dq_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
-                         dout.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
-                         dq_bshd.data_ptr(), B, H, HKV, S, (float)scale, stq,
-                         cur_stream());
-        fa_bwd_dkv_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
-                          dout.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
-                          dk32.data_ptr(), dv32.data_ptr(), B, H, HKV, S,
-                          (float)scale, stq, cur_stream());
-      }
-      auto dk = at::empty({B, HKV, S, D}, k.options());
-      auto dv = at::empty({B, HKV, S, D}, v.options());
-      f32_to_bf16_launch(dk32.data_ptr(), dk.data_ptr(), dk32.numel(),
-                         cur_stream());
-      f32_to_bf16_launch(dv32.data_ptr(), dv.data_ptr(), dv32.numel(),
-                         cur_stream());
-      return {dq, dk, dv};
-    }
+  auto dvec = at::empty({s.B, s.H, s.S}, q.options().dtype(at::kFloat));
+  long long ost[3], dstr[3];
+  pack_strides(ost, out, 0);
+  pack_strides(dstr, dout, 0);
+  fa_bwd_pre_launch(dout.data_ptr(), out.data_ptr(), dvec.data_ptr(), s.B,
+                    s.H, s.S, ost, dstr, attn_stream());
+  // dq mirrors q's layout: allocate [B,S,H,D] storage, return as view
+  auto dq_bshd = at::empty({s.B, s.S, s.H, s.D}, q.options());
+  auto dq = dq_bshd.permute({0, 2, 1, 3});
+  // the kernels use ONE strides triple for both q loads and dq stores, so
+  // stage q into dq's layout if they differ
+  at::Tensor quse = q;
+  if (q.strides() != dq.strides()) {
+    quse = at::empty({s.B, s.S, s.H, s.D}, q.options()).permute({0, 2, 1, 3});
+    quse.copy_(q);
   }
+  long long st[12];
+  pack_strides(st, quse, 0);
+  pack_strides(st, k, 3);
+  pack_strides(st, v, 6);
+  pack_strides(st, dout, 9);
+  auto dk32 =
+      at::zeros({s.B, s.HKV, s.S, s.D}, k.options().dtype(at::kFloat));
+  auto dv32 =
+      at::zeros({s.B, s.HKV, s.S, s.D}, v.options().dtype(at::kFloat));
+  if (attn_use_v3(s.S)) {
+    fa_bwd_dq_v3_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
+                        dout.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
+                        dq_bshd.data_ptr(), s.B, s.H, s.HKV, s.S,
+                        (float)scale, st, doc_ptr(doc_start), attn_stream());
+    fa_bwd_dkv_v3_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
+                         dout.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
+                         dk32.data_ptr(), dv32.data_ptr(), s.B, s.H, s.HKV,
+                         s.S, (float)scale, st, doc_ptr(doc_end),
+                         attn_stream());
+  } else {
+    fa_bwd_dq_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
+                     dout.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
+                     dq_bshd.data_ptr(), s.B, s.H, s.HKV, s.S, (float)scale,
+                     st, attn_stream());
+    fa_bwd_dkv_launch(quse.data_ptr(), k.data_ptr(), v.data_ptr(),
+                      dout.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
+                      dk32.data_ptr(), dv32.data_ptr(), s.B, s.H, s.HKV, s.S,
+                      (float)scale, st, attn_stream());
+  }
+  auto dk = at::empty({s.B, s.HKV, s.S, s.D}, k.options());
+  auto dv = at::empty({s.B, s.HKV, s.S, s.D}, v.options());
+  f32_to_bf16_launch(dk32.data_ptr(), dk.data_ptr(), dk32.numel(),
+                     attn_stream());
+  f32_to_bf16_launch(dv32.data_ptr(), dv.data_ptr(), dv32.numel(),
+                     attn_stream());
+  return {dq, dk, dv};
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_bwd(
@@ -512,9 +468,6 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flash_attn_doc_bwd(
     const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
     const at::Tensor& out, const at::Tensor& dout, const at::Tensor& lse,
     double scale, const at::Tensor& doc_start, const at::Tensor& doc_end) {
-  check_attn_view(q, "q");
-  check_doc_arg(doc_start, q, "doc_start");
-  check_doc_arg(doc_end, q, "doc_end");
   return flash_attn_bwd_impl(q, k, v, out, dout, lse, scale, &doc_start,
                              &doc_end);
 }

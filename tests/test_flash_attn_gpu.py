@@ -60,6 +60,79 @@ def test_flash_bwd_matches_autograd():
     torch.testing.assert_close(v.grad.float(), v2.grad, rtol=5e-2, atol=5e-2)
 
 
+@pytest.mark.parametrize("S", [64, 192])
+def test_flash_16x16_fwd_bwd_matches_ref(S):
+    """S % 256 != 0 runs the 16x16 kernels in both directions. S=64 is one
+    tile (diagonal only); S=192 is three, so the off-diagonal tiles and the
+    running rescale run too. HKV < H: two heads add into one dK/dV."""
+    from dlrover_amd.ops import flash_attention
+
+    torch.manual_seed(2)
+    B, H, HKV, D = 1, 4, 2, 128
+    scale = 1 / math.sqrt(D)
+    q = torch.randn(B, H, S, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+    k = torch.randn(B, HKV, S, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+    v = torch.randn(B, HKV, S, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+    dout = torch.randn(B, H, S, D, device="cuda", dtype=torch.bfloat16)
+
+    out = flash_attention(q, k, v, scale)
+    out.backward(dout)
+
+    q2 = q.detach().float().requires_grad_(True)
+    k2 = k.detach().float().requires_grad_(True)
+    v2 = v.detach().float().requires_grad_(True)
+    ref = _ref(q2, k2, v2, scale)
+    ref.backward(dout.float())
+
+    torch.testing.assert_close(out.float(), ref.detach(), rtol=2e-2, atol=2e-2)
+    torch.testing.assert_close(q.grad.float(), q2.grad, rtol=5e-2, atol=5e-2)
+    torch.testing.assert_close(k.grad.float(), k2.grad, rtol=5e-2, atol=5e-2)
+    torch.testing.assert_close(v.grad.float(), v2.grad, rtol=5e-2, atol=5e-2)
+
+
+def test_flash_bwd_argument_checks():
+    """Every bad argument is refused by a check made before anything is
+    allocated or launched."""
+    from dlrover_amd.ops.api import hip_ops
+
+    torch.manual_seed(3)
+    scale = 1 / math.sqrt(128)
+
+    def mk(B, H, HKV, S, D):
+        return (
+            torch.randn(B, H, S, D, device="cuda", dtype=torch.bfloat16),
+            torch.randn(B, HKV, S, D, device="cuda", dtype=torch.bfloat16),
+            torch.randn(B, HKV, S, D, device="cuda", dtype=torch.bfloat16),
+        )
+
+    q, k, v = mk(1, 4, 2, 64, 128)
+    out, lse = hip_ops().flash_attn_fwd(q, k, v, scale)
+    dout = torch.randn_like(out)
+    assert lse.shape == (1, 4, 64)
+
+    def bwd(q=q, k=k, v=v, out=out, dout=dout, lse=lse):
+        return hip_ops().flash_attn_bwd(q, k, v, out, dout, lse, scale)
+
+    # the binding's message for each bad argument: the error must come from
+    # its check, not from a kernel that ran on the bad input
+    bad = [
+        (dict(lse=lse.double()), "lse must be fp32"),
+        (dict(lse=lse.transpose(1, 2).contiguous()), r"lse must be contiguous \[B, H, S\]"),
+        (dict(dout=torch.randn(1, 4, 128, 128, device="cuda", dtype=torch.bfloat16)),
+         "dout must have q's shape"),
+        (dict(zip("qkv", mk(1, 4, 2, 64, 64))), "head_dim must be 128"),
+        (dict(zip("qkv", mk(1, 4, 2, 96, 128))), "multiple of 64"),
+        (dict(zip("qkv", mk(1, 3, 2, 64, 128))), "H % HKV"),
+    ]
+    for kw, message in bad:
+        with pytest.raises(RuntimeError, match=message):
+            bwd(**kw)
+    torch.cuda.synchronize()
+    # the valid arguments still pass
+    dq, dk, dv = bwd()
+    assert dq.shape == q.shape and dk.shape == k.shape and dv.shape == v.shape
+
+
 def test_flash_attn_in_model_trains():
     """Tiny-8B-shaped config (D=128) trains with the flash path."""
     from dlrover_amd.models import LlamaConfig, LlamaForCausalLM
