@@ -22,6 +22,9 @@ from dlrover_amd.ops.api import (  # noqa: F401
     doc_positions,
     doc_start_from_eos,
     doc_start_from_ids,
+    fp8_block_dequantize,
+    fp8_block_quantize,
+    fused_adamw_fp8_multi_step,
     fused_adamw_multi_step,
     fused_adamw_step,
     grad_sq_norm,

@@ -45,6 +45,21 @@ across that group would be counted once per rank.
 
 The new arguments live on the optimizer object, not in ``param_groups``, so
 checkpoints keep their format.
+
+Opt-in FP8 moments (``moments="fp8"``, implies the batched path): a parameter
+with ``ndim >= 2`` and a last dim that is a multiple of 256 — decided from
+the global shape, so every FSDP2 rank decides alike — keeps both moments as
+OCP e4m3fn codes with one fp32 scale per 256 consecutive elements
+(ops/csrc/adamw_fp8.hip). Its state is ``master_param`` (fp32), ``exp_avg``
+(uint8 codes, the local parameter's shape), ``exp_avg_scale`` (fp32
+``[rows..., cols/256]``), ``exp_avg_sq_root`` / ``exp_avg_sq_root_scale``
+(the same for the SQUARE ROOT of the second moment) and ``step``: 6.03 bytes
+per parameter instead of 12. Every tensor keeps the parameter's dim 0, so the
+state reshards like any other. All other parameters keep fp32 moments on the
+multi-tensor path. ``load_state_dict`` converts between the two formats, so
+either kind of checkpoint loads into either kind of optimizer. A non-finite
+gradient that is not caught by ``max_grad_norm`` poisons its whole 256-block
+(through the block scale) instead of one element.
 """
 
 import logging
@@ -53,6 +68,10 @@ from typing import Iterable, Optional
 import torch
 
 from dlrover_amd.ops.api import (
+    FP8_BLOCK,
+    fp8_block_dequantize,
+    fp8_block_quantize,
+    fused_adamw_fp8_multi_step,
     fused_adamw_multi_step,
     fused_adamw_step,
     grad_sq_norm,
@@ -88,7 +107,10 @@ class FusedAdamW(torch.optim.Optimizer):
         multi_tensor: bool = False,
         skip_nonfinite: bool = True,
         grad_norm_group=None,
+        moments: str = "fp32",
     ):
+        if moments not in ("fp32", "fp8"):
+            raise ValueError(f'moments must be "fp32" or "fp8", got {moments!r}')
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -100,7 +122,10 @@ class FusedAdamW(torch.optim.Optimizer):
         self.max_grad_norm = max_grad_norm
         self.skip_nonfinite = skip_nonfinite
         self.grad_norm_group = grad_norm_group
-        self._batched = multi_tensor or max_grad_norm is not None
+        self.moments = moments
+        self._batched = (
+            multi_tensor or max_grad_norm is not None or moments == "fp8"
+        )
         # 0-dim fp32 tensor on the params' device: global pre-clip norm of
         # the last step (None until a clipped step has run)
         self.last_grad_norm: Optional[torch.Tensor] = None
@@ -108,6 +133,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._ws_partials = None
         self._ws_norm_sq = None
         self._span_elems = 0  # 0 = automatic
+        self._span_elems_fp8 = 0  # same, a multiple of 256
         self._reduce_group_cache = None
         self._warned_no_capture = False
 
@@ -116,8 +142,33 @@ class FusedAdamW(torch.optim.Optimizer):
         state["step"] = 0
         master = _local(p.detach()).float().clone()
         state["master_param"] = master
+        if self._fp8_eligible(p):
+            scale_shape = (*master.shape[:-1], master.shape[-1] // FP8_BLOCK)
+            for k in ("exp_avg", "exp_avg_sq_root"):
+                state[k] = torch.zeros_like(master, dtype=torch.uint8)
+                state[k + "_scale"] = master.new_zeros(scale_shape)
+            return
         state["exp_avg"] = torch.zeros_like(master)
         state["exp_avg_sq"] = torch.zeros_like(master)
+
+    def _fp8_eligible(self, p: torch.Tensor) -> bool:
+        """FP8 moments for this parameter? From the GLOBAL shape only (a
+        DTensor's ``shape``), so every rank of a Shard(0) placement decides
+        alike, one that holds 0 rows included."""
+        return (
+            self.moments == "fp8"
+            and p.ndim >= 2
+            and p.shape[-1] % FP8_BLOCK == 0
+        )
+
+    def state_nbytes(self) -> int:
+        """Bytes of all optimizer state tensors (the local shards)."""
+        return sum(
+            v.numel() * v.element_size()
+            for st in self.state.values()
+            for v in st.values()
+            if torch.is_tensor(v)
+        )
 
     def _one_step(self):
         for group in self.param_groups:
@@ -201,7 +252,7 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _mt_step(self):
         """Batched path: [global norm ->] one multi-tensor update per
-        (param group, gradient dtype). No host sync."""
+        (param group, gradient dtype, moment format). No host sync."""
         if self.max_grad_norm is not None:
             # refuse an unsupported layout before any state is touched
             self._norm_reduce_group(
@@ -221,25 +272,47 @@ class FusedAdamW(torch.optim.Optimizer):
                 g = _local(p.grad).contiguous()
                 p_data = _local(p.data)
                 is_bf16 = p.dtype == torch.bfloat16
-                b = by_dtype.setdefault(g.dtype, ([], [], [], [], [], []))
+                fp8 = "exp_avg_sq_root" in state
+                b = by_dtype.setdefault(
+                    (g.dtype, fp8), ([], [], [], [], [], [], [], [])
+                )
                 b[0].append(state["master_param"])
                 b[1].append(g)
                 b[2].append(state["exp_avg"])
-                b[3].append(state["exp_avg_sq"])
+                b[3].append(state["exp_avg_sq_root" if fp8 else "exp_avg_sq"])
                 b[4].append(p_data if is_bf16 else None)
                 b[5].append(state["step"])
+                if fp8:
+                    b[6].append(state["exp_avg_scale"])
+                    b[7].append(state["exp_avg_sq_root_scale"])
                 grads.append(g)
                 params.append(p)
                 if not is_bf16:
                     fp32_copies.append((p_data, state["master_param"]))
-            batches.extend((group, b) for b in by_dtype.values())
+            batches.extend((group, k[1], b) for k, b in by_dtype.items())
         if not grads:
             return
         norm_sq = None
         if self.max_grad_norm is not None:
             norm_sq = self._global_norm_sq(grads, params)
-        for group, b in batches:
+        for group, fp8, b in batches:
             n = len(b[0])
+            if fp8:
+                fused_adamw_fp8_multi_step(
+                    b[0], b[1], b[2], b[6], b[3], b[7], b[4],
+                    [group["lr"]] * n,
+                    [group["weight_decay"]] * n,
+                    b[5],
+                    group["betas"][0],
+                    group["betas"][1],
+                    group["eps"],
+                    1.0,
+                    norm_sq,
+                    self.max_grad_norm if norm_sq is not None else float("inf"),
+                    self.skip_nonfinite,
+                    self._span_elems_fp8,
+                )
+                continue
             fused_adamw_multi_step(
                 b[0], b[1], b[2], b[3], b[4],
                 [group["lr"]] * n,
@@ -352,7 +425,8 @@ class FusedAdamW(torch.optim.Optimizer):
                 dev = _local(p).device
                 cur = self.state.get(p, {})
                 entry = {}
-                for k, v in state_dict["state"][sid].items():
+                saved = self._convert_moments(p, state_dict["state"][sid], dev)
+                for k, v in saved.items():
                     if torch.is_tensor(v):
                         # copy INTO existing state storage when shapes match:
                         # a fresh .to(dev) would double-allocate ~96 GB of
@@ -378,6 +452,33 @@ class FusedAdamW(torch.optim.Optimizer):
         for g, sg in zip(groups, saved_groups):
             g.update({k: v for k, v in sg.items() if k != "params"})
         self._graph = None  # state tensors moved: any captured graph is stale
+
+    def _convert_moments(self, p, saved: dict, dev) -> dict:
+        """A saved state entry in the moment format this optimizer keeps for
+        ``p``: fp32 moments are quantised (``exp_avg_sq`` through its square
+        root), FP8 moments are dequantised (and the root squared). An entry
+        that already has the right format is returned as it is."""
+        has_fp8 = "exp_avg_sq_root" in saved
+        want_fp8 = self._fp8_eligible(p)
+        if has_fp8 == want_fp8 or "exp_avg" not in saved:
+            return saved
+        out = dict(saved)
+        if want_fp8:
+            m = out.pop("exp_avg").to(dev).float()
+            root = out.pop("exp_avg_sq").to(dev).float().sqrt()
+            out["exp_avg"], out["exp_avg_scale"] = fp8_block_quantize(m)
+            out["exp_avg_sq_root"], out["exp_avg_sq_root_scale"] = (
+                fp8_block_quantize(root)
+            )
+        else:
+            out["exp_avg"] = fp8_block_dequantize(
+                out.pop("exp_avg").to(dev), out.pop("exp_avg_scale").to(dev)
+            )
+            out["exp_avg_sq"] = fp8_block_dequantize(
+                out.pop("exp_avg_sq_root").to(dev),
+                out.pop("exp_avg_sq_root_scale").to(dev),
+            ).square_()
+        return out
 
     def zero_grad(self, set_to_none: bool = True):
         # torch semantics by default: dropping grads lets backward ASSIGN the

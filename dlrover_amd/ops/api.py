@@ -868,6 +868,139 @@ def fused_adamw_multi_step(
 
 
 # ---------------------------------------------------------------------------
+# FP8 block-scaled optimizer moments
+#
+# A block is 256 consecutive elements of a contiguous tensor whose last dim
+# is a multiple of 256. Per block: scale = absmax / 448 (fp32 division),
+# code = RNE_e4m3fn(x / scale) stored as uint8, dequant = float(code) * scale.
+# A block whose scale would be below the smallest normal fp32 (absmax under
+# about 5.3e-36, the all-zero block included) is flushed: scale 0, codes 0. A
+# subnormal scale has too few bits to keep x / scale within +-448. A NaN or
+# inf element makes the scale NaN or inf, and with it its whole block.
+# ---------------------------------------------------------------------------
+
+FP8_BLOCK = 256
+FP8_E4M3_MAX = 448.0
+FP8_MIN_SCALE = 1.1754943508222875e-38  # FLT_MIN
+
+
+def _fp8_blocks(t: torch.Tensor) -> torch.Tensor:
+    if t.dim() < 1 or t.shape[-1] % FP8_BLOCK:
+        raise ValueError(
+            f"fp8 blocks: the last dim must be a multiple of {FP8_BLOCK}, "
+            f"got shape {tuple(t.shape)}"
+        )
+    return t.reshape(*t.shape[:-1], t.shape[-1] // FP8_BLOCK, FP8_BLOCK)
+
+
+def fp8_block_quantize(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 ``[..., C]`` -> ``(codes, scales)``: OCP e4m3fn bit patterns as
+    uint8 ``[..., C]`` (``codes.view(torch.float8_e4m3fn)`` decodes them) and
+    fp32 scales ``[..., C/256]``, by the definition above."""
+    x = x.detach().float().contiguous()
+    xb = _fp8_blocks(x)
+    if _use_hip(x):
+        return tuple(hip_ops().fp8_block_quantize(x))
+    # CPU reference: the definition
+    scales = xb.abs().amax(-1) / FP8_E4M3_MAX
+    # degenerate blocks are flushed; a NaN scale is not below FP8_MIN_SCALE
+    scales = torch.where(scales < FP8_MIN_SCALE, torch.zeros_like(scales), scales)
+    s = scales.unsqueeze(-1)
+    y = torch.where(s != 0, xb / s, torch.zeros_like(xb))
+    codes = y.to(torch.float8_e4m3fn).view(torch.uint8).reshape(x.shape)
+    return codes, scales
+
+
+def fp8_block_dequantize(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """Inverse of ``fp8_block_quantize``: fp32 ``float(code) * scale``."""
+    cb = _fp8_blocks(codes)
+    if _use_hip(codes, scales):
+        return hip_ops().fp8_block_dequantize(codes.contiguous(), scales.contiguous())
+    vals = cb.contiguous().view(torch.float8_e4m3fn).float() * scales.unsqueeze(-1)
+    return vals.reshape(codes.shape)
+
+
+def fused_adamw_fp8_multi_step(
+    masters,
+    grads,
+    exp_avgs,
+    exp_avg_scales,
+    exp_avg_sq_roots,
+    exp_avg_sq_root_scales,
+    params_bf16,
+    lrs,
+    weight_decays,
+    steps,
+    beta1: float,
+    beta2: float,
+    eps: float,
+    grad_scale: float = 1.0,
+    norm_sq: Optional[torch.Tensor] = None,
+    max_norm: float = float("inf"),
+    skip_nonfinite: bool = True,
+    span_elems: int = 0,
+):
+    """``fused_adamw_multi_step`` on FP8 block-scaled moments: ``exp_avgs``
+    and ``exp_avg_sq_roots`` are uint8 e4m3fn codes shaped like their master,
+    with one fp32 scale per 256-block; the second moment is kept as its
+    square root. Every master's last dim must be a multiple of 256.
+
+    The update uses the fresh fp32 moments; quantisation error enters only
+    through the state the next step loads. Clipping and the non-finite skip
+    work as in ``fused_adamw_multi_step``. ``span_elems`` (0 = automatic) is
+    a multiple of 256."""
+    masters = list(masters)
+    if not masters:
+        return
+    if params_bf16 is None:
+        params_bf16 = [None] * len(masters)
+    if masters[0].is_cuda:
+        hip_ops().multi_tensor_adamw_fp8(
+            masters,
+            [g.contiguous() for g in grads],
+            list(exp_avgs),
+            list(exp_avg_scales),
+            list(exp_avg_sq_roots),
+            list(exp_avg_sq_root_scales),
+            list(params_bf16),
+            [float(x) for x in lrs],
+            [float(x) for x in weight_decays],
+            [int(x) for x in steps],
+            beta1,
+            beta2,
+            eps,
+            grad_scale,
+            norm_sq,
+            max_norm,
+            skip_nonfinite,
+            span_elems,
+        )
+        return
+    # CPU reference: the fp32 reference step on the dequantised state, then
+    # the definition of the format
+    if norm_sq is not None and skip_nonfinite:
+        if not bool(torch.isfinite(norm_sq.detach().reshape(-1)[0])):
+            return
+    ms = [fp8_block_dequantize(c, s) for c, s in zip(exp_avgs, exp_avg_scales)]
+    vs = [
+        fp8_block_dequantize(c, s).square_()
+        for c, s in zip(exp_avg_sq_roots, exp_avg_sq_root_scales)
+    ]
+    fused_adamw_multi_step(
+        masters, grads, ms, vs, params_bf16, lrs, weight_decays, steps,
+        beta1, beta2, eps, grad_scale, norm_sq, max_norm, skip_nonfinite,
+    )
+    for i in range(len(masters)):
+        for x, codes, scales in (
+            (ms[i], exp_avgs[i], exp_avg_scales[i]),
+            (vs[i].sqrt_(), exp_avg_sq_roots[i], exp_avg_sq_root_scales[i]),
+        ):
+            c, s = fp8_block_quantize(x)
+            codes.copy_(c)
+            scales.copy_(s)
+
+
+# ---------------------------------------------------------------------------
 # checkpoint integrity: per-tensor checksums, fused pack / unpack
 # ---------------------------------------------------------------------------
 

@@ -51,6 +51,16 @@ void mt_adamw_launch(int, void* const*, const void* const*, void* const*,
                      const float*, const float*, const int*, int, float,
                      float, float, float, const float*, float, int, long long,
                      void*);
+int f8_max_tensors();
+int f8_block_elems();
+long long f8_auto_span(long long);
+void f8_quantize_launch(const float*, void*, float*, long long, void*);
+void f8_dequantize_launch(const void*, const float*, float*, long long, void*);
+void f8_adamw_launch(int, void* const*, const void* const*, void* const*,
+                     void* const*, void* const*, void* const*, void* const*,
+                     const long long*, const float*, const float*, const int*,
+                     int, float, float, float, float, const float*, float,
+                     int, long long, void*);
 int ckpt_span_quantum();
 int ckpt_max_blocks();
 long long ckpt_auto_span(long long);
@@ -717,6 +727,139 @@ void multi_tensor_adamw(
                   skip_nonfinite ? 1 : 0, span, cur_stream());
 }
 
+// ---- FP8 block-scaled moments (adamw_fp8.hip) -----------------------------
+// Scales of a [..., C] tensor (C a multiple of the block) are [..., C / block].
+std::vector<int64_t> f8_scale_sizes(const at::Tensor& t) {
+  const int64_t block = f8_block_elems();
+  TORCH_CHECK(t.dim() >= 1 && t.size(-1) % block == 0,
+              "fp8 blocks: the last dim must be a multiple of ", block);
+  auto sizes = t.sizes().vec();
+  sizes.back() /= block;
+  return sizes;
+}
+
+bool aligned16(const at::Tensor& t) {
+  return t.numel() == 0 || ((uintptr_t)t.data_ptr() & 15u) == 0;
+}
+
+// codes (uint8, x's shape) and scales (fp32) of one state tensor
+void check_f8_pair(const at::Tensor& codes, const at::Tensor& scales,
+                   const char* name) {
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte &&
+                  codes.is_contiguous() && aligned16(codes),
+              name, " codes must be contiguous, 16-byte aligned uint8 on GPU");
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == at::kFloat &&
+                  scales.is_contiguous() &&
+                  scales.sizes().vec() == f8_scale_sizes(codes),
+              name, " scales must be contiguous fp32 on GPU, one per block");
+}
+
+std::tuple<at::Tensor, at::Tensor> fp8_block_quantize(const at::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat &&
+                  x.is_contiguous() && aligned16(x),
+              "fp8_block_quantize: x must be contiguous, 16-byte aligned fp32 "
+              "on GPU");
+  auto codes = at::empty(x.sizes(), x.options().dtype(at::kByte));
+  auto scales = at::empty(f8_scale_sizes(x), x.options());
+  f8_quantize_launch((const float*)x.data_ptr(), codes.data_ptr(),
+                     (float*)scales.data_ptr(), scales.numel(), cur_stream());
+  return {codes, scales};
+}
+
+at::Tensor fp8_block_dequantize(const at::Tensor& codes,
+                                const at::Tensor& scales) {
+  check_f8_pair(codes, scales, "fp8_block_dequantize:");
+  auto out = at::empty(codes.sizes(), scales.options());
+  f8_dequantize_launch(codes.data_ptr(), (const float*)scales.data_ptr(),
+                       (float*)out.data_ptr(), scales.numel(), cur_stream());
+  return out;
+}
+
+void multi_tensor_adamw_fp8(
+    const std::vector<at::Tensor>& masters,
+    const std::vector<at::Tensor>& grads,
+    const std::vector<at::Tensor>& exp_avgs,
+    const std::vector<at::Tensor>& exp_avg_scales,
+    const std::vector<at::Tensor>& exp_avg_sq_roots,
+    const std::vector<at::Tensor>& exp_avg_sq_root_scales,
+    c10::optional<std::vector<c10::optional<at::Tensor>>> params_bf16,
+    const std::vector<double>& lrs, const std::vector<double>& weight_decays,
+    const std::vector<int64_t>& steps, double beta1, double beta2, double eps,
+    double grad_scale, c10::optional<at::Tensor> norm_sq, double max_norm,
+    bool skip_nonfinite, int64_t span_elems) {
+  const size_t n = masters.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n &&
+                  exp_avg_scales.size() == n && exp_avg_sq_roots.size() == n &&
+                  exp_avg_sq_root_scales.size() == n && lrs.size() == n &&
+                  weight_decays.size() == n && steps.size() == n &&
+                  (!params_bf16.has_value() || params_bf16->size() == n),
+              "multi_tensor_adamw_fp8: list lengths differ");
+  if (n == 0) return;
+  const int64_t block = f8_block_elems();
+  TORCH_CHECK(span_elems >= 0 && span_elems % block == 0 &&
+                  span_elems < (1LL << 31),
+              "span_elems must be 0 (automatic) or a positive multiple of ",
+              block, " below 2^31");
+  const auto numel = mt_numels(masters);
+  long long span = span_elems;
+  if (span == 0) {
+    long long total = 0;
+    for (long long k : numel) total += k;
+    span = f8_auto_span(total);
+  }
+  const bool gbf16 = grads[0].scalar_type() == at::kBFloat16;
+  std::vector<void*> pm(n), pe(n), pes(n), pr(n), prs(n), pb(n, nullptr);
+  std::vector<const void*> pg(n);
+  std::vector<float> lr(n), wd(n);
+  std::vector<int> st(n);
+  for (size_t i = 0; i < n; ++i) {
+    const auto& p = masters[i];
+    const auto& g = grads[i];
+    TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat &&
+                    p.is_contiguous() && aligned16(p),
+                "master param must be contiguous, 16-byte aligned fp32 on GPU");
+    check_f8_pair(exp_avgs[i], exp_avg_scales[i], "exp_avg");
+    check_f8_pair(exp_avg_sq_roots[i], exp_avg_sq_root_scales[i],
+                  "exp_avg_sq_root");
+    TORCH_CHECK(exp_avgs[i].sizes() == p.sizes() &&
+                    exp_avg_sq_roots[i].sizes() == p.sizes(),
+                "moment codes must have the master param's shape");
+    TORCH_CHECK(g.is_cuda() && g.is_contiguous(), "grad must be GPU");
+    TORCH_CHECK(g.numel() == p.numel(), "grad/param numel mismatch");
+    TORCH_CHECK(g.scalar_type() == (gbf16 ? at::kBFloat16 : at::kFloat),
+                "grads of one call must all be bf16 or all be fp32");
+    pm[i] = p.data_ptr();
+    pg[i] = g.data_ptr();
+    pe[i] = exp_avgs[i].data_ptr();
+    pes[i] = exp_avg_scales[i].data_ptr();
+    pr[i] = exp_avg_sq_roots[i].data_ptr();
+    prs[i] = exp_avg_sq_root_scales[i].data_ptr();
+    if (params_bf16.has_value() && (*params_bf16)[i].has_value()) {
+      const auto& b = *(*params_bf16)[i];
+      check_bf16(b, "param_bf16");
+      TORCH_CHECK(b.numel() == p.numel(), "param_bf16 numel mismatch");
+      pb[i] = b.data_ptr();
+    }
+    lr[i] = (float)lrs[i];
+    wd[i] = (float)weight_decays[i];
+    st[i] = (int)steps[i];
+  }
+  const float* nsq = nullptr;
+  if (norm_sq.has_value()) {
+    TORCH_CHECK(norm_sq->is_cuda() && norm_sq->scalar_type() == at::kFloat &&
+                    norm_sq->numel() >= 1,
+                "norm_sq must be fp32 on GPU");
+    nsq = (const float*)norm_sq->data_ptr();
+  }
+  TORCH_CHECK(mt_num_blocks((int)n, numel.data(), span) < (1LL << 31),
+              "multi_tensor_adamw_fp8: too many spans");
+  f8_adamw_launch((int)n, pm.data(), pg.data(), pe.data(), pes.data(),
+                  pr.data(), prs.data(), pb.data(), numel.data(), lr.data(),
+                  wd.data(), st.data(), gbf16 ? 1 : 0, (float)beta1,
+                  (float)beta2, (float)eps, (float)grad_scale, nsq,
+                  (float)max_norm, skip_nonfinite ? 1 : 0, span, cur_stream());
+}
+
 // ---- checkpoint pack / unpack / checksum (ckpt_pack.hip) ------------------
 // span_bytes == 0 picks the span from the list's total size; any other value
 // must be a multiple of the block's trip (threads x 16 bytes).
@@ -882,6 +1025,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("beta2"), py::arg("eps"), py::arg("grad_scale"),
         py::arg("norm_sq"), py::arg("max_norm"), py::arg("skip_nonfinite"),
         py::arg("span_elems") = 0);
+  m.attr("F8_MAX_TENSORS") = f8_max_tensors();
+  m.attr("F8_BLOCK") = f8_block_elems();
+  m.def("fp8_block_quantize", &fp8_block_quantize,
+        "fp32 [..., C] -> (e4m3fn codes as uint8 [..., C], fp32 scales "
+        "[..., C/256]); scale = absmax/448 per 256-block",
+        py::arg("x"));
+  m.def("fp8_block_dequantize", &fp8_block_dequantize,
+        "(codes, scales) of fp8_block_quantize -> fp32", py::arg("codes"),
+        py::arg("scales"));
+  m.def("multi_tensor_adamw_fp8", &multi_tensor_adamw_fp8,
+        "batched fused AdamW on FP8 block-scaled moments (exp_avg and "
+        "sqrt(exp_avg_sq)) with an optional device-side clip coefficient",
+        py::arg("masters"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_scales"), py::arg("exp_avg_sq_roots"),
+        py::arg("exp_avg_sq_root_scales"), py::arg("params_bf16"),
+        py::arg("lrs"), py::arg("weight_decays"), py::arg("steps"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("grad_scale"), py::arg("norm_sq"), py::arg("max_norm"),
+        py::arg("skip_nonfinite"), py::arg("span_elems") = 0);
   m.attr("CKPT_SPAN_QUANTUM") = ckpt_span_quantum();
   m.attr("CKPT_MAX_BLOCKS") = ckpt_max_blocks();
   m.def("ckpt_auto_span", [](int64_t total) {

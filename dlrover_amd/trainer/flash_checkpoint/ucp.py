@@ -11,7 +11,10 @@ cut this rank's new slice — done streaming per old shard file so peak memory
 is one full model+optimizer copy.
 
 Optimizer state (FusedAdamW master/exp_avg/exp_avg_sq) shards exactly like
-its parameter, so the same concat+slice applies positionally.
+its parameter, so the same concat+slice applies positionally. With
+``FusedAdamW(moments="fp8")`` the keys are exp_avg / exp_avg_sq_root (uint8
+e4m3 codes) and their ``*_scale`` tensors (fp32, one per 256 elements of a
+row): every one keeps the parameter's dim 0, so they reshard the same way.
 """
 
 import glob

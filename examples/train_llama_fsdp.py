@@ -39,6 +39,10 @@ def main():
     p.add_argument("--grad-clip", type=float, default=0.0,
                    help="clip the global gradient norm at this value inside "
                         "the fused optimizer (0 = off)")
+    p.add_argument("--optim-moments", choices=("fp32", "fp8"), default="fp32",
+                   help="fp8: keep the Adam moments of every weight whose "
+                        "last dim is a multiple of 256 as e4m3 codes with "
+                        "per-256-element scales (half the checkpointed state)")
     p.add_argument("--act-ckpt", action="store_true",
                    help="recompute transformer blocks in backward")
     p.add_argument("--doc-len", type=int, default=0,
@@ -92,7 +96,8 @@ def main():
             fully_shard(blk)
         fully_shard(model)
     clip_kw = {"max_grad_norm": args.grad_clip} if args.grad_clip > 0 else {}
-    opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=0.1, **clip_kw)
+    opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=0.1,
+                     moments=args.optim_moments, **clip_kw)
     trainer = ElasticTrainer(model)
 
     cp = FsdpShardCheckpointer(
