@@ -54,6 +54,27 @@ class LlamaConfig:
     # for long-seq / big-batch on 288 GB HBM3E only when activations would
     # not otherwise fit
     activation_checkpointing: bool = False
+    # "bf16": plain nn.Linear projections. "fp8": qkv_proj, o_proj,
+    # gate_up_proj and down_proj are ops.Fp8Linear — the same bf16 parameters
+    # (state dicts and checkpoints are interchangeable), FP8 GEMM operands
+    # with one current absmax scale per tensor. lm_head and embed stay as
+    # they are. Opt-in; README "The hot path" has the measurements
+    linear_precision: str = "bf16"
+
+    def __post_init__(self):
+        if self.linear_precision not in ("bf16", "fp8"):
+            raise ValueError(
+                "linear_precision must be 'bf16' or 'fp8', got "
+                f"{self.linear_precision!r}"
+            )
+        if self.linear_precision == "fp8":
+            from dlrover_amd.ops import fp8_linear_supported
+
+            if not fp8_linear_supported():
+                raise RuntimeError(
+                    "linear_precision='fp8': torch._scaled_mm rejects the FP8 "
+                    "products on this device; use linear_precision='bf16'"
+                )
 
     @property
     def head_dim(self) -> int:
@@ -116,15 +137,24 @@ class RMSNorm(nn.Module):
         return rmsnorm(x, self.weight, self.eps)
 
 
+def _linear_cls(cfg: "LlamaConfig"):
+    if cfg.linear_precision == "fp8":
+        from dlrover_amd.ops import Fp8Linear
+
+        return Fp8Linear
+    return nn.Linear
+
+
 class Attention(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
         self.cfg = cfg
         d, hd = cfg.hidden_size, cfg.head_dim
-        self.qkv_proj = nn.Linear(
+        linear = _linear_cls(cfg)
+        self.qkv_proj = linear(
             d, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd, bias=cfg.attn_bias
         )
-        self.o_proj = nn.Linear(cfg.n_heads * hd, d, bias=False)
+        self.o_proj = linear(cfg.n_heads * hd, d, bias=False)
 
     def forward(self, x, pos, cos, sin, doc_start=None):
         """doc_start [B,S] int32 (optional): packed-sequence document mask —
@@ -205,10 +235,11 @@ class Attention(nn.Module):
 class MLP(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
-        self.gate_up_proj = nn.Linear(
+        linear = _linear_cls(cfg)
+        self.gate_up_proj = linear(
             cfg.hidden_size, 2 * cfg.intermediate_size, bias=False
         )
-        self.down_proj = nn.Linear(cfg.intermediate_size, cfg.hidden_size, bias=False)
+        self.down_proj = linear(cfg.intermediate_size, cfg.hidden_size, bias=False)
 
     def forward(self, x):
         return self.down_proj(swiglu(self.gate_up_proj(x)))

@@ -9,6 +9,10 @@ Loading policy (the framework's hot path must actually run native code):
     against these same references.
 """
 
+# Importing the submodule binds the name ``fp8_linear`` in this package to the
+# module; the import from ``api`` below rebinds it to the function, which is
+# what ``dlrover_amd.ops.fp8_linear`` means to callers. Keep this order.
+from dlrover_amd.ops.fp8_linear import Fp8Linear  # noqa: F401
 from dlrover_amd.ops.api import (  # noqa: F401
     ExtensionMissingError,
     causal_softmax,
@@ -24,6 +28,9 @@ from dlrover_amd.ops.api import (  # noqa: F401
     doc_start_from_ids,
     fp8_block_dequantize,
     fp8_block_quantize,
+    fp8_linear,
+    fp8_linear_supported,
+    fp8_quantize,
     fused_adamw_fp8_multi_step,
     fused_adamw_multi_step,
     fused_adamw_step,

@@ -920,6 +920,224 @@ def fp8_block_dequantize(codes: torch.Tensor, scales: torch.Tensor) -> torch.Ten
     return vals.reshape(codes.shape)
 
 
+# ---------------------------------------------------------------------------
+# FP8 linear layers: tensor-wise scaled GEMM operands
+#
+# "Current" scaling of a 2-D tensor t[R, C] (bf16 or fp32), one scale per
+# tensor, by the convention of the block quantiser above: FMAX is 448 for
+# e4m3 (float8_e4m3fn) and 57344 for e5m2; scale = absmax(t) / FMAX (fp32
+# division, NaN-propagating absmax); a scale below FLT_MIN (the all-zero
+# tensor included) is flushed to 0 with all codes 0; otherwise
+# code = RNE(float(t) / scale) and the dequantised value is
+# float(code) * scale. An inf or NaN element makes the scale inf or NaN, and
+# since the scale multiplies every output of a product, a non-finite input
+# gives a non-finite output everywhere. The scale is a 1-element fp32 tensor
+# on the tensor's device; nothing is read on the host.
+#
+# The GEMM is the library's (torch._scaled_mm, a row-major and b
+# column-major), so the dgrad and wgrad products need transposed codes; the
+# HIP cast kernel writes both layouts from one read of the tensor.
+# ---------------------------------------------------------------------------
+
+FP8_FORMATS = {
+    "e4m3": (torch.float8_e4m3fn, 448.0),
+    "e5m2": (torch.float8_e5m2, 57344.0),
+}
+
+# calls of fp8_linear that took plain F.linear because M, N or K is not a
+# multiple of 16
+fp8_linear_fallbacks = 0
+
+_FP8_MM_OK = {}
+
+
+def _fp8_format(fmt: str):
+    try:
+        return FP8_FORMATS[fmt]
+    except KeyError:
+        raise ValueError(f"fp8 format must be 'e4m3' or 'e5m2', got {fmt!r}") from None
+
+
+def fp8_quantize(
+    t: torch.Tensor,
+    fmt: str = "e4m3",
+    rowwise: bool = True,
+    colwise: bool = False,
+    scale: Optional[torch.Tensor] = None,
+    partials: Optional[torch.Tensor] = None,
+):
+    """``t[R, C]`` (bf16 or fp32) -> ``(codes | None, codes_t | None, scale)``.
+
+    ``codes`` is ``[R, C]`` (``rowwise``) and ``codes_t`` ``[C, R]``, the same
+    codes transposed (``colwise``), both ``torch.float8_*`` and contiguous:
+    ``codes`` is a ready ``a`` operand of ``torch._scaled_mm`` and
+    ``codes_t.t()`` a ready ``b`` operand. ``scale`` is the 1-element fp32
+    scale by the definition above; pass a saved one to reuse it without a
+    second absmax pass.
+
+    GPU: a two-stage absmax (no atomics; ``partials`` is its int32 workspace
+    of ``hip_ops().fp8_amax_slots(t)`` elements, allocated here when omitted)
+    and one cast kernel that reads ``t`` once for both layouts. No host sync.
+    CPU: the definition in torch ops."""
+    dtype, fmax = _fp8_format(fmt)
+    if t.dim() != 2:
+        raise ValueError(f"fp8_quantize: expected a 2-D tensor, got {tuple(t.shape)}")
+    if t.shape[0] % 16 or t.shape[1] % 16 or t.numel() == 0:
+        raise ValueError(
+            "fp8_quantize: both dimensions must be positive multiples of 16, "
+            f"got {tuple(t.shape)}"
+        )
+    if t.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"fp8_quantize: expected bf16 or fp32, got {t.dtype}")
+    if scale is not None and (scale.dtype != torch.float32 or scale.numel() != 1):
+        raise ValueError("fp8_quantize: scale must be a 1-element fp32 tensor")
+    t = t.detach()
+    if _use_hip(t):
+        ext = hip_ops()
+        t = t.contiguous()
+        if t.data_ptr() % 16:  # a view at an odd offset: the kernels load 16 B
+            t = t.clone()
+        if scale is None:
+            scale = torch.empty(1, device=t.device, dtype=torch.float32)
+            if partials is None:
+                partials = torch.empty(
+                    ext.fp8_amax_slots(t), device=t.device, dtype=torch.int32
+                )
+            ext.fp8_amax_scale(t, fmt, partials, scale)
+        else:
+            scale = scale.reshape(1)
+        codes, codes_t = ext.fp8_cast_transpose(t, scale, fmt, rowwise, colwise)
+        return (
+            codes.view(dtype) if codes is not None else None,
+            codes_t.view(dtype) if codes_t is not None else None,
+            scale,
+        )
+    # CPU reference: the definition
+    tf = t.float()
+    if scale is None:
+        scale = (tf.abs().amax() / fmax).reshape(1)
+        # a NaN scale is not below FP8_MIN_SCALE
+        scale = torch.where(scale < FP8_MIN_SCALE, torch.zeros_like(scale), scale)
+    else:
+        scale = scale.reshape(1)
+    y = torch.where(scale != 0, tf / scale, torch.zeros_like(tf))
+    codes = y.to(dtype)
+    return (
+        codes if rowwise else None,
+        codes.t().contiguous() if colwise else None,
+        scale,
+    )
+
+
+def _fp8_mm(a, b, scale_a, scale_b, out_dtype):
+    """``(a * scale_a) @ (b * scale_b)``: ``a`` fp8 row-major, ``b`` e4m3
+    column-major. GPU: the library's scaled GEMM. CPU: an fp32 matmul of the
+    dequantised operands, rounded to ``out_dtype`` (the oracle)."""
+    if a.is_cuda:
+        return torch._scaled_mm(
+            a, b, scale_a=scale_a, scale_b=scale_b, out_dtype=out_dtype,
+            use_fast_accum=False,
+        )
+    return ((a.float() * scale_a) @ (b.float() * scale_b)).to(out_dtype)
+
+
+def fp8_linear_supported(
+    grad_format: str = "e5m2", device: Optional[torch.device] = None
+) -> bool:
+    """Whether ``torch._scaled_mm`` takes the products ``fp8_linear`` needs on
+    this device: e4m3 x e4m3 (forward) and ``grad_format`` x e4m3 (backward).
+    One 16x16x16 product each, run once and cached. A rejection by the library
+    is a Python exception; that is all this guards against. The CPU path
+    needs no scaled GEMM and is always supported."""
+    _fp8_format(grad_format)
+    if device is None:
+        if not torch.cuda.is_available():
+            return True
+        device = "cuda"
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return True
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    ok = True
+    for fmt in ("e4m3", grad_format):
+        key = (index, fmt)
+        if key not in _FP8_MM_OK:
+            try:
+                a = torch.ones(16, 16, device=dev).to(FP8_FORMATS[fmt][0])
+                b = torch.ones(16, 16, device=dev).to(torch.float8_e4m3fn)
+                one = torch.ones(1, device=dev)
+                _fp8_mm(a, b.t(), one, one, torch.bfloat16)
+                _FP8_MM_OK[key] = True
+            except Exception:  # noqa: BLE001 - any rejection by the library
+                _FP8_MM_OK[key] = False
+        ok = ok and _FP8_MM_OK[key]
+    return ok
+
+
+class _Fp8Linear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, grad_format):
+        K = x.shape[-1]
+        N = weight.shape[0]
+        xq, xq_t, sx = fp8_quantize(x.reshape(-1, K), "e4m3", True, True)
+        wq, _, sw = fp8_quantize(weight, "e4m3", True, False)
+        y = _fp8_mm(xq, wq.t(), sx, sw, x.dtype)
+        # the weight itself, not its codes: under FSDP2 the unsharded weight
+        # is freed between forward and backward, a saved 8-bit copy would
+        # keep 1 byte per parameter of every layer alive
+        ctx.save_for_backward(xq_t, sx, sw, weight)
+        ctx.grad_format = grad_format
+        return y.view(*x.shape[:-1], N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xq_t, sx, sw, weight = ctx.saved_tensors
+        N, K = weight.shape
+        lead = dy.shape[:-1]
+        gq, gq_t, sg = fp8_quantize(
+            dy.reshape(-1, N), ctx.grad_format, True, ctx.needs_input_grad[1]
+        )
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            # the forward's scale: no second absmax over the weight
+            _, wq_t, _ = fp8_quantize(weight, "e4m3", False, True, scale=sw)
+            dx = _fp8_mm(gq, wq_t.t(), sg, sw, dy.dtype).view(*lead, K)
+        if ctx.needs_input_grad[1]:
+            dw = _fp8_mm(gq_t, xq_t.t(), sg, sx, weight.dtype)
+        return dx, dw, None
+
+
+def fp8_linear(
+    x: torch.Tensor,
+    weight: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+    grad_format: str = "e5m2",
+) -> torch.Tensor:
+    """``F.linear`` with FP8 GEMM operands: ``x`` (flattened to ``[M, K]``)
+    and ``weight[N, K]`` as e4m3, the output gradient as ``grad_format``, each
+    with one current absmax scale; accumulation in fp32, outputs in the input
+    dtypes. The bias is a separate add; its gradient is the plain sum.
+
+    If M, N or K is not a multiple of 16 the call is plain ``F.linear`` and
+    ``fp8_linear_fallbacks`` counts it."""
+    global fp8_linear_fallbacks
+    _fp8_format(grad_format)
+    N, K = weight.shape
+    M = x.numel() // K if K else 0
+    if M % 16 or N % 16 or K % 16 or M == 0 or N == 0:
+        fp8_linear_fallbacks += 1
+        return torch.nn.functional.linear(x, weight, bias)
+    if x.is_cuda and not fp8_linear_supported(grad_format, x.device):
+        raise RuntimeError(
+            "fp8_linear: torch._scaled_mm rejects the e4m3 x e4m3 or "
+            f"{grad_format} x e4m3 product on this device"
+        )
+    y = _Fp8Linear.apply(x, weight, grad_format)
+    if bias is not None:
+        y = y + bias
+    return y
+
+
 def fused_adamw_fp8_multi_step(
     masters,
     grads,

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "attention_launch.h"
+#include "fp8_cast_launch.h"
 
 extern "C" {
 void rmsnorm_fwd_launch(const void*, const void*, void*, void*, int, int,
@@ -860,6 +861,70 @@ void multi_tensor_adamw_fp8(
                   (float)max_norm, skip_nonfinite ? 1 : 0, span, cur_stream());
 }
 
+// ---- FP8 tensor-wise cast for the linear layers (fp8_cast.hip) -----------
+// x: [R, C] bf16 or fp32, contiguous, 16-byte aligned, R and C multiples of 16
+bool check_fp8_cast_input(const at::Tensor& x, const char* op) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() && aligned16(x),
+              op, ": x must be a contiguous, 16-byte aligned 2-D GPU tensor");
+  TORCH_CHECK(x.size(0) % 16 == 0 && x.size(1) % 16 == 0 && x.numel() > 0,
+              op, ": both dimensions must be positive multiples of 16");
+  const bool bf16 = x.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf16 || x.scalar_type() == at::kFloat, op,
+              ": x must be bf16 or fp32");
+  return bf16;
+}
+
+int fp8_fmt_code(const std::string& fmt) {
+  TORCH_CHECK(fmt == "e4m3" || fmt == "e5m2", "fp8 format must be 'e4m3' or "
+              "'e5m2', got '", fmt, "'");
+  return fmt == "e5m2" ? FP8_FMT_E5M2 : FP8_FMT_E4M3;
+}
+
+void check_fp8_scale(const at::Tensor& scale, const at::Tensor& x) {
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat &&
+                  scale.numel() == 1 && scale.device() == x.device(),
+              "fp8 scale must be a 1-element fp32 tensor on x's device");
+}
+
+int64_t fp8_amax_slots(const at::Tensor& x) {
+  return fp8_amax_num_partials((long long)x.numel(),
+                               x.scalar_type() == at::kBFloat16);
+}
+
+// scale[0] = absmax(x) / FMAX; partials: int32 workspace of fp8_amax_slots(x)
+void fp8_amax_scale(const at::Tensor& x, const std::string& fmt,
+                    at::Tensor& partials, at::Tensor& scale) {
+  const bool bf16 = check_fp8_cast_input(x, "fp8_amax_scale");
+  check_fp8_scale(scale, x);
+  const long long need = fp8_amax_num_partials((long long)x.numel(), bf16);
+  TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
+                  partials.scalar_type() == at::kInt &&
+                  partials.numel() >= need,
+              "fp8_amax_scale: partials must be contiguous int32 on GPU with "
+              "at least ", need, " elements");
+  fp8_amax_scale_launch(x.data_ptr(), (long long)x.numel(), bf16,
+                        fp8_fmt_code(fmt), (unsigned int*)partials.data_ptr(),
+                        (float*)scale.data_ptr(), (hipStream_t)cur_stream());
+}
+
+// (codes [R, C] | None, codes_t [C, R] | None) as uint8
+std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>>
+fp8_cast_transpose(const at::Tensor& x, const at::Tensor& scale,
+                   const std::string& fmt, bool rowwise, bool colwise) {
+  const bool bf16 = check_fp8_cast_input(x, "fp8_cast_transpose");
+  check_fp8_scale(scale, x);
+  c10::optional<at::Tensor> codes, codes_t;
+  const int64_t R = x.size(0), C = x.size(1);
+  if (rowwise) codes = at::empty({R, C}, x.options().dtype(at::kByte));
+  if (colwise) codes_t = at::empty({C, R}, x.options().dtype(at::kByte));
+  fp8_cast_transpose_launch(
+      x.data_ptr(), (const float*)scale.data_ptr(),
+      rowwise ? codes->data_ptr() : nullptr,
+      colwise ? codes_t->data_ptr() : nullptr, R, C, bf16, fp8_fmt_code(fmt),
+      (hipStream_t)cur_stream());
+  return {codes, codes_t};
+}
+
 // ---- checkpoint pack / unpack / checksum (ckpt_pack.hip) ------------------
 // span_bytes == 0 picks the span from the list's total size; any other value
 // must be a multiple of the block's trip (threads x 16 bytes).
@@ -1046,6 +1111,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("skip_nonfinite"), py::arg("span_elems") = 0);
   m.attr("CKPT_SPAN_QUANTUM") = ckpt_span_quantum();
   m.attr("CKPT_MAX_BLOCKS") = ckpt_max_blocks();
+  m.def("fp8_amax_slots", &fp8_amax_slots,
+        "int32 partial slots fp8_amax_scale needs for this tensor",
+        py::arg("x"));
+  m.def("fp8_amax_scale", &fp8_amax_scale,
+        "scale[0] = absmax(x) / FMAX of the format (0 below FLT_MIN, NaN and "
+        "inf propagate): two kernels over the partials workspace, no atomics",
+        py::arg("x"), py::arg("fmt"), py::arg("partials"), py::arg("scale"));
+  m.def("fp8_cast_transpose", &fp8_cast_transpose,
+        "RNE(x / scale) as OCP fp8 codes, row-major and/or transposed, from "
+        "one read of x",
+        py::arg("x"), py::arg("scale"), py::arg("fmt"), py::arg("rowwise"),
+        py::arg("colwise"));
   m.def("ckpt_auto_span", [](int64_t total) {
     return (int64_t)ckpt_auto_span((long long)total);
   }, "span in bytes that ckpt_copy_sum picks for a list of this total size");

@@ -13,6 +13,7 @@ workers, and training resumes from the latest committed checkpoint.
 """
 
 import argparse
+import dataclasses
 import json
 import os
 import signal
@@ -43,6 +44,11 @@ def main():
                    help="fp8: keep the Adam moments of every weight whose "
                         "last dim is a multiple of 256 as e4m3 codes with "
                         "per-256-element scales (half the checkpointed state)")
+    p.add_argument("--linear", choices=("bf16", "fp8"), default="bf16",
+                   help="fp8: the qkv, o, gate_up and down projections run "
+                        "their GEMMs on FP8 operands (e4m3 activations and "
+                        "weights, e5m2 gradients, one current scale per "
+                        "tensor); parameters and checkpoints stay bf16")
     p.add_argument("--act-ckpt", action="store_true",
                    help="recompute transformer blocks in backward")
     p.add_argument("--doc-len", type=int, default=0,
@@ -79,7 +85,8 @@ def main():
     )
     if args.model == "tiny":
         args.seq = min(args.seq, cfg.max_seq_len)
-    cfg.activation_checkpointing = args.act_ckpt
+    cfg = dataclasses.replace(cfg, activation_checkpointing=args.act_ckpt,
+                              linear_precision=args.linear)
     with device:
         model = LlamaForCausalLM(cfg)
     model = model.to(device)
@@ -162,7 +169,9 @@ def main():
 
     cp.wait_latest_checkpoint()
     if rank == 0:
-        print(f"[train] done at step {args.steps} loss={loss.item():.4f}",
+        peak = (f" peak_allocated={torch.cuda.max_memory_allocated() / 2**30:.2f}GiB"
+                if use_gpu else "")
+        print(f"[train] done at step {args.steps} loss={loss.item():.4f}{peak}",
               flush=True)
     dist.barrier()
     dist.destroy_process_group()

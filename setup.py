@@ -25,6 +25,7 @@ sources = [
     os.path.join(CSRC, "adamw.hip"),
     os.path.join(CSRC, "multi_tensor.hip"),
     os.path.join(CSRC, "adamw_fp8.hip"),
+    os.path.join(CSRC, "fp8_cast.hip"),
     os.path.join(CSRC, "ckpt_pack.hip"),
     os.path.join(CSRC, "softmax.hip"),
     os.path.join(CSRC, "cross_entropy.hip"),
