@@ -494,21 +494,37 @@ def ctypes_addr(buf: memoryview) -> int:
     return ctypes.addressof(ctypes.c_char.from_buffer(buf))
 
 
+class _BouncedDrain:
+    """What drain_async returns when the drain still has host work to do:
+    synchronize() does it (see _DeviceStager._drain_bounced)."""
+
+    def __init__(self, stager: "_DeviceStager", dst: torch.Tensor):
+        self._stager = stager
+        self._dst = dst
+
+    def synchronize(self):
+        self._stager._drain_bounced(self._dst)
+
+
 class _DeviceStager:
     """Persistent GPU staging buffer + side-stream D2H drain.
 
     snapshot(): device-to-device copies of every tensor into one flat
     buffer — the only part that blocks training (multi-TB/s HBM3E).
     drain_async(): one contiguous D2H copy to the shm mapping on a
-    dedicated stream, overlapped with subsequent training compute.
+    dedicated stream, overlapped with subsequent training compute; where
+    the mapping could not be page-locked, the same bytes through two
+    pinned bounce buffers, driven by the thread that waits for the drain.
     If the full payload won't fit in free HBM, falls back to chunked
     staging (blocking bounded by PCIe instead).
     """
 
     CHUNK = 2 << 30  # 2 GiB chunks for the fallback path
+    BOUNCE = 256 << 20  # each of the two pinned buffers of _drain_bounced
 
     def __init__(self):
         self._buf: Optional[torch.Tensor] = None
+        self._bounce: Optional[List[torch.Tensor]] = None
         self._stream = torch.cuda.Stream()
         self._payload = 0
         self._chunked = False
@@ -607,13 +623,49 @@ class _DeviceStager:
                 self._sums[: self._n_sums], non_blocking=True
             )
 
-    def drain_async(self, host_view: np.ndarray, pinned: bool) -> torch.cuda.Event:
+    def _drain_bounced(self, dst: torch.Tensor):
+        """Drain staging[0:payload) into an shm mapping that could not be
+        page-locked: D2H on the drain stream into one of two pinned bounce
+        buffers while the host copies the other into the mapping. Runs on
+        the thread that waits for the drain, never on the training thread."""
+        if self._bounce is None:
+            self._bounce = [
+                torch.empty(self.BOUNCE, dtype=torch.uint8, pin_memory=True)
+                for _ in range(2)
+            ]
+        chunks = [
+            (c0, min(self._payload, c0 + self.BOUNCE))
+            for c0 in range(0, self._payload, self.BOUNCE)
+        ]
+        landed = [torch.cuda.Event(), torch.cuda.Event()]
+        with torch.cuda.stream(self._stream):
+
+            def fetch(i):
+                c0, c1 = chunks[i]
+                self._bounce[i % 2][: c1 - c0].copy_(
+                    self._buf[c0:c1], non_blocking=True
+                )
+                landed[i % 2].record(self._stream)
+
+            if chunks:
+                fetch(0)
+            for i, (c0, c1) in enumerate(chunks):
+                if i + 1 < len(chunks):
+                    # its buffer held chunk i-1, which the host has copied
+                    fetch(i + 1)
+                landed[i % 2].synchronize()
+                dst[c0:c1].copy_(self._bounce[i % 2][: c1 - c0])
+            self._drain_sums()
+        self._stream.synchronize()
+
+    def drain_async(self, host_view: np.ndarray, pinned: bool):
+        """Returns an object whose synchronize() returns once the snapshot
+        is in host_view."""
         evt = torch.cuda.Event()
         dst = torch.from_numpy(host_view)
         if not self._chunked:
-            with torch.cuda.stream(self._stream):
-                ok = False
-                if pinned:
+            if pinned:
+                with torch.cuda.stream(self._stream):
                     # direct hipMemcpyAsync into the REGISTERED shm mapping:
                     # torch's copy_ does not recognize foreign-pinned memory
                     # and degrades to a synchronous null-stream hipMemcpy
@@ -625,18 +677,16 @@ class _DeviceStager:
                         hip_ops().memcpy_d2h_async(
                             host_view.ctypes.data, self._buf[: self._payload]
                         )
-                        ok = True
+                        self._drain_sums()
+                        evt.record(self._stream)
+                        return evt
                     except Exception:  # noqa: BLE001 — never lose the ckpt
                         logger.exception(
-                            "async D2H fast path failed; torch fallback"
+                            "async D2H fast path failed; bounce fallback"
                         )
-                if not ok:
-                    dst[: self._payload].copy_(
-                        self._buf[: self._payload], non_blocking=False
-                    )
-                self._drain_sums()
-                evt.record(self._stream)
-            return evt
+            # a D2H copy into pageable memory would hold the caller for the
+            # whole drain: the waiter takes it through pinned buffers
+            return _BouncedDrain(self, dst)
         # chunked fallback: serialize tensor copies through the small buffer.
         # The sources are the LIVE tensors (no full device snapshot exists),
         # so this path must complete before training resumes — synchronize

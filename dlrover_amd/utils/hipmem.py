@@ -4,7 +4,9 @@ Flash checkpoint's D2H drain wants the POSIX shm mapping page-locked so
 `hipMemcpyAsync` runs at full PCIe gen5 rate and truly async (ref premise:
 flash_checkpoint.md:68-71 quotes ~32 GB/s PCIe4; MI355X is gen5 ~63 GB/s).
 torch can't pin foreign memory, so we register the mapping directly with the
-HIP runtime. Falls back cleanly when no GPU / no libamdhip64 is present.
+HIP runtime. Falls back cleanly when no GPU / no libamdhip64 is present, or
+when the runtime refuses (it does in some virtual machines): the caller then
+drains through pinned buffers of its own (shm_handler._DeviceStager).
 """
 
 import ctypes
@@ -33,6 +35,8 @@ def _hip() -> Optional[ctypes.CDLL]:
         _lib.hipHostRegister.restype = ctypes.c_int
         _lib.hipHostUnregister.argtypes = [ctypes.c_void_p]
         _lib.hipHostUnregister.restype = ctypes.c_int
+        _lib.hipGetLastError.argtypes = []
+        _lib.hipGetLastError.restype = ctypes.c_int
     return _lib
 
 
@@ -43,12 +47,18 @@ def host_register(ptr: int, nbytes: int) -> bool:
         return False
     rc = lib.hipHostRegister(ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 0)
     if rc != 0:
-        logger.warning("hipHostRegister(%d bytes) failed rc=%d — D2H will be pageable", nbytes, rc)
+        # the runtime keeps a failed call as this thread's last error, and
+        # the next launch (torch checks it after each one) would report it
+        # as its own: take it out here, where it is handled
+        lib.hipGetLastError()
+        logger.warning(
+            "hipHostRegister(%d bytes) failed rc=%d — D2H goes through a "
+            "pinned bounce buffer", nbytes, rc)
         return False
     return True
 
 
 def host_unregister(ptr: int) -> None:
     lib = _hip()
-    if lib is not None:
-        lib.hipHostUnregister(ctypes.c_void_p(ptr))
+    if lib is not None and lib.hipHostUnregister(ctypes.c_void_p(ptr)) != 0:
+        lib.hipGetLastError()  # as in host_register

@@ -302,6 +302,40 @@ def test_snapshot_bytes_identical_to_unfused():
         h_off.unlink()
 
 
+def test_bounced_drain_in_several_chunks(monkeypatch):
+    """A mapping that is not page-locked is drained through the two pinned
+    bounce buffers. With 1 MiB buffers the ~6 MB payload takes six chunks,
+    the last one partial, each buffer reused; the CPU tensors that lie
+    between the GPU tensors keep their bytes."""
+    from dlrover_amd.trainer.flash_checkpoint.shm_handler import (
+        SharedMemoryHandler,
+        _DeviceStager,
+        _get_by_path,
+    )
+
+    monkeypatch.delenv("DLROVER_CKPT_FORCE_CHUNKED", raising=False)
+    monkeypatch.setattr(_DeviceStager, "BOUNCE", 1 << 20)
+    state = _tiny_train_state()
+    h = SharedMemoryHandler(
+        f"ckint_bounce_{os.getpid()}_{time.time_ns()}", host_pin=False,
+        checksum=True,
+    )
+    try:
+        h.save_state_dict(4, state, block=False)
+        h.wait_drained()
+        assert not h._stager._chunked
+        assert h._stager._payload > 5 * _DeviceStager.BOUNCE
+        assert h._stager._payload % _DeviceStager.BOUNCE
+        meta = h.read_meta()
+        assert meta is not None and meta.step == 4
+        for tm in meta.tensors:
+            want = _bytes_of(_get_by_path(state, tm.path))
+            assert _payload_bytes(h, tm) == want.numpy().tobytes(), tm.path
+            assert tuple(tm.checksum) == ckpt_checksum_ref(want), tm.path
+    finally:
+        h.unlink()
+
+
 def test_restore_into_verified(tmp_path, monkeypatch):
     """restore_into with checksums on a GPU: device load + device-side
     verification + device-to-device copies; a corrupt shm snapshot falls
