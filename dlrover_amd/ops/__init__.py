@@ -32,15 +32,19 @@ from dlrover_amd.ops.api import (  # noqa: F401
     fp8_linear_supported,
     fp8_quantize,
     fused_adamw_fp8_multi_step,
+    fused_adamw_fp8_sr_multi_step,
     fused_adamw_multi_step,
+    fused_adamw_sr_multi_step,
     fused_adamw_step,
     grad_sq_norm,
     hip_ops,
     hip_ops_available,
+    philox4x32_10,
     rmsnorm,
     rmsnorm_add,
     rope_ref,
     rope_rotate,
+    stochastic_round_bf16,
     swiglu,
     validate_doc_start,
     vocab_parallel_cross_entropy,

@@ -60,6 +60,24 @@ multi-tensor path. ``load_state_dict`` converts between the two formats, so
 either kind of checkpoint loads into either kind of optimizer. A non-finite
 gradient that is not caught by ``max_grad_norm`` poisons its whole 256-block
 (through the block scale) instead of one element.
+
+Opt-in master-free update (``master_weights=False``, implies the batched
+path): a bf16 parameter keeps no ``master_param``. The update is computed in
+fp32 from the bf16 weight and rounded back stochastically
+(ops/csrc/adamw_sr.hip; the rounding and its Philox4x32-10 noise are defined
+in ops/api.py), so updates far below one bf16 ulp still move the weights in
+expectation. Its state is ``step`` and the moments in whichever format
+``moments`` selects: 8 (fp32 moments) or 2.03 (FP8) bytes per parameter, with
+the 2-byte weight itself now the only copy. fp32 parameters are their own
+master and are handled as before. The noise depends on ``sr_seed``, the
+parameter's ordinal in the flattened ``param_groups``, its step and the
+element index, never on the launch split or the rank; ``sr_seed`` lives on
+the object, so a resumed run must pass the same seed to continue the same
+noise sequence. ``capture_graph=True`` is refused: a replayed graph freezes
+the step into its kernel arguments, and the same noise every step is a bias,
+not rounding. ``load_state_dict`` converts both ways: a saved ``master_param``
+is written into the bf16 weight (round-to-nearest-even) and dropped, a
+missing one is created from the weight.
 """
 
 import logging
@@ -72,7 +90,9 @@ from dlrover_amd.ops.api import (
     fp8_block_dequantize,
     fp8_block_quantize,
     fused_adamw_fp8_multi_step,
+    fused_adamw_fp8_sr_multi_step,
     fused_adamw_multi_step,
+    fused_adamw_sr_multi_step,
     fused_adamw_step,
     grad_sq_norm,
     grad_sq_norm_slots,
@@ -108,9 +128,17 @@ class FusedAdamW(torch.optim.Optimizer):
         skip_nonfinite: bool = True,
         grad_norm_group=None,
         moments: str = "fp32",
+        master_weights: bool = True,
+        sr_seed: int = 0,
     ):
         if moments not in ("fp32", "fp8"):
             raise ValueError(f'moments must be "fp32" or "fp8", got {moments!r}')
+        if capture_graph and not master_weights:
+            raise ValueError(
+                "master_weights=False cannot be combined with capture_graph: "
+                "the rounding noise is keyed on the step, which a replayed "
+                "graph freezes into its kernel arguments"
+            )
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -123,8 +151,13 @@ class FusedAdamW(torch.optim.Optimizer):
         self.skip_nonfinite = skip_nonfinite
         self.grad_norm_group = grad_norm_group
         self.moments = moments
+        self.master_weights = master_weights
+        self.sr_seed = int(sr_seed)
         self._batched = (
-            multi_tensor or max_grad_norm is not None or moments == "fp8"
+            multi_tensor
+            or max_grad_norm is not None
+            or moments == "fp8"
+            or not master_weights
         )
         # 0-dim fp32 tensor on the params' device: global pre-clip norm of
         # the last step (None until a clipped step has run)
@@ -141,7 +174,8 @@ class FusedAdamW(torch.optim.Optimizer):
         state = self.state[p]
         state["step"] = 0
         master = _local(p.detach()).float().clone()
-        state["master_param"] = master
+        if not self._master_free(p):
+            state["master_param"] = master
         if self._fp8_eligible(p):
             scale_shape = (*master.shape[:-1], master.shape[-1] // FP8_BLOCK)
             for k in ("exp_avg", "exp_avg_sq_root"):
@@ -160,6 +194,12 @@ class FusedAdamW(torch.optim.Optimizer):
             and p.ndim >= 2
             and p.shape[-1] % FP8_BLOCK == 0
         )
+
+    def _master_free(self, p: torch.Tensor) -> bool:
+        """No fp32 master for this parameter? bf16 parameters of a
+        ``master_weights=False`` optimizer; an fp32 parameter is its own
+        master either way."""
+        return not self.master_weights and p.dtype == torch.bfloat16
 
     def state_nbytes(self) -> int:
         """Bytes of all optimizer state tensors (the local shards)."""
@@ -260,23 +300,27 @@ class FusedAdamW(torch.optim.Optimizer):
                  if p.grad is not None]
             )
         batches, grads, params, fp32_copies = [], [], [], []
+        ordinal = -1  # position in the flattened param_groups: the SR stream
         for group in self.param_groups:
             by_dtype = {}
             for p in group["params"]:
+                ordinal += 1
                 if p.grad is None:
                     continue
                 state = self.state[p]
-                if "master_param" not in state:
+                if "step" not in state:
                     self._init_state(p)
                 state["step"] += 1
                 g = _local(p.grad).contiguous()
                 p_data = _local(p.data)
                 is_bf16 = p.dtype == torch.bfloat16
                 fp8 = "exp_avg_sq_root" in state
+                sr = "master_param" not in state
                 b = by_dtype.setdefault(
-                    (g.dtype, fp8), ([], [], [], [], [], [], [], [])
+                    (g.dtype, fp8, sr), ([], [], [], [], [], [], [], [], [])
                 )
-                b[0].append(state["master_param"])
+                # master-free: the bf16 weight stands in the master's place
+                b[0].append(p_data if sr else state["master_param"])
                 b[1].append(g)
                 b[2].append(state["exp_avg"])
                 b[3].append(state["exp_avg_sq_root" if fp8 else "exp_avg_sq"])
@@ -285,18 +329,46 @@ class FusedAdamW(torch.optim.Optimizer):
                 if fp8:
                     b[6].append(state["exp_avg_scale"])
                     b[7].append(state["exp_avg_sq_root_scale"])
+                b[8].append(ordinal)
                 grads.append(g)
                 params.append(p)
                 if not is_bf16:
                     fp32_copies.append((p_data, state["master_param"]))
-            batches.extend((group, k[1], b) for k, b in by_dtype.items())
+            batches.extend((group, k[1], k[2], b) for k, b in by_dtype.items())
         if not grads:
             return
         norm_sq = None
         if self.max_grad_norm is not None:
             norm_sq = self._global_norm_sq(grads, params)
-        for group, fp8, b in batches:
+        for group, fp8, sr, b in batches:
             n = len(b[0])
+            if sr:
+                clip = (
+                    1.0,
+                    norm_sq,
+                    self.max_grad_norm if norm_sq is not None else float("inf"),
+                    self.skip_nonfinite,
+                )
+                hyper = (
+                    [group["lr"]] * n,
+                    [group["weight_decay"]] * n,
+                    b[5],
+                    b[8],
+                    group["betas"][0],
+                    group["betas"][1],
+                    group["eps"],
+                    self.sr_seed,
+                )
+                if fp8:
+                    fused_adamw_fp8_sr_multi_step(
+                        b[0], b[1], b[2], b[6], b[3], b[7], *hyper, *clip,
+                        self._span_elems_fp8,
+                    )
+                else:
+                    fused_adamw_sr_multi_step(
+                        b[0], b[1], b[2], b[3], *hyper, *clip, self._span_elems
+                    )
+                continue
             if fp8:
                 fused_adamw_fp8_multi_step(
                     b[0], b[1], b[2], b[6], b[3], b[7], b[4],
@@ -426,6 +498,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 cur = self.state.get(p, {})
                 entry = {}
                 saved = self._convert_moments(p, state_dict["state"][sid], dev)
+                saved = self._convert_master(p, saved, dev)
                 for k, v in saved.items():
                     if torch.is_tensor(v):
                         # copy INTO existing state storage when shapes match:
@@ -478,6 +551,22 @@ class FusedAdamW(torch.optim.Optimizer):
                 out.pop("exp_avg_sq_root").to(dev),
                 out.pop("exp_avg_sq_root_scale").to(dev),
             ).square_()
+        return out
+
+    def _convert_master(self, p, saved: dict, dev) -> dict:
+        """A saved state entry with or without ``master_param``, as this
+        optimizer keeps ``p``. Master-free: a saved master is written into
+        the parameter's local shard (round-to-nearest-even, the value the
+        master-weight path itself left there) and dropped. With masters: a
+        missing one is the fp32 of the weight."""
+        has_master = "master_param" in saved
+        if has_master != self._master_free(p) or "step" not in saved:
+            return saved
+        out = dict(saved)
+        if has_master:
+            _local(p.data).copy_(out.pop("master_param").to(dev))
+        else:
+            out["master_param"] = _local(p.detach()).float().clone()
         return out
 
     def zero_grad(self, set_to_none: bool = True):

@@ -1219,6 +1219,206 @@ def fused_adamw_fp8_multi_step(
 
 
 # ---------------------------------------------------------------------------
+# stochastic rounding to bf16, and AdamW without fp32 master weights
+#
+# Rounding: for a finite fp32 value w with bit pattern u and a uniform 16-bit
+# integer r in [0, 65535], the bf16 result has the bit pattern (u + r) >> 16,
+# one 32-bit unsigned add that cannot wrap for finite w. So
+# P(round away from zero) = (u & 0xFFFF) / 65536 and a value that is exactly
+# a bf16 never moves; the largest finite values can round to inf, which is
+# correct stochastic rounding. inf and NaN (exponent all ones) get no noise:
+# inf keeps its bits, a NaN keeps its sign and upper payload bits and has its
+# quiet bit set, so it stays a NaN.
+#
+# Noise: counter-based, a function of (seed, stream, step, element index i)
+# and never of grid, span, launch split or wave. r of element i is 16-bit
+# half i % 8 of the 128-bit output of Philox4x32-10, i.e. word (i % 8) // 2,
+# low half when i is even and high half when odd, for the counter
+# (lo32(i // 8), hi32(i // 8), step, stream) and the key
+# (lo32(seed), hi32(seed)). Philox4x32 is the textbook one: 10 rounds,
+# multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and
+# 0xBB67AE85. In the optimizer, stream is the parameter's ordinal in the
+# flattened param_groups and step its state["step"] after the increment.
+# ---------------------------------------------------------------------------
+
+_M32 = 0xFFFFFFFF
+
+
+def _mul_hi_lo(a: int, b: torch.Tensor):
+    """(hi32, lo32) of the 64-bit product of a 32-bit constant and 32-bit
+    values held in int64, through two 48-bit partial products."""
+    p_lo = a * (b & 0xFFFF)
+    p_hi = a * (b >> 16)
+    lo = (p_lo + ((p_hi & 0xFFFF) << 16)) & _M32
+    hi = (p_hi + (p_lo >> 16)) >> 16
+    return hi, lo
+
+
+def philox4x32_10(counter: torch.Tensor, key) -> torch.Tensor:
+    """Philox4x32-10 of ``counter[..., 4]`` under ``key[2]`` (32-bit values
+    in int64) -> ``[..., 4]`` int64 holding the four 32-bit output words. A
+    torch-int64 CPU reference, the oracle of the device generator."""
+    c = [counter[..., j].to(torch.int64) & _M32 for j in range(4)]
+    k0, k1 = (int(k) & _M32 for k in key)
+    for _ in range(10):
+        hi0, lo0 = _mul_hi_lo(0xD2511F53, c[0])
+        hi1, lo1 = _mul_hi_lo(0xCD9E8D57, c[2])
+        c = [hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0]
+        k0 = (k0 + 0x9E3779B9) & _M32
+        k1 = (k1 + 0xBB67AE85) & _M32
+    return torch.stack(c, dim=-1)
+
+
+def stochastic_round_bf16(
+    x: torch.Tensor, seed: int, stream: int = 0, step: int = 0
+) -> torch.Tensor:
+    """``x`` (read as fp32) -> bf16 of the same shape by the definition
+    above; the element index is the index in the contiguous tensor. GPU: one
+    HIP kernel, one Philox call per 8 elements. CPU: the definition in torch
+    ops. Both give the same bits."""
+    seed = int(seed) & ((1 << 64) - 1)
+    xf = x.detach().float().contiguous()
+    if _use_hip(xf):
+        out = torch.empty_like(xf, dtype=torch.bfloat16)
+        hip_ops().sr_round(xf, out, seed, int(stream), int(step))
+        return out
+    n = xf.numel()
+    u = xf.reshape(-1).view(torch.int32).to(torch.int64) & _M32
+    group = torch.arange((n + 7) // 8, dtype=torch.int64)
+    counter = torch.stack(
+        [group & _M32, group >> 32, torch.full_like(group, int(step)),
+         torch.full_like(group, int(stream))], dim=-1,
+    )
+    words = philox4x32_10(counter, (seed & _M32, seed >> 32))
+    r = torch.stack([words & 0xFFFF, words >> 16], dim=-1).reshape(-1)[:n]
+    special = (u >> 16) | torch.where((u & 0x7FFFFF) != 0, 0x40, 0)
+    bits = torch.where((u & 0x7F800000) == 0x7F800000, special, (u + r) >> 16)
+    # 16-bit patterns -> the int16 with those bits
+    out = ((bits ^ 0x8000) - 0x8000).to(torch.int16).view(torch.bfloat16)
+    return out.reshape(x.shape)
+
+
+def fused_adamw_sr_multi_step(
+    params,
+    grads,
+    exp_avgs,
+    exp_avg_sqs,
+    lrs,
+    weight_decays,
+    steps,
+    streams,
+    beta1: float,
+    beta2: float,
+    eps: float,
+    seed: int,
+    grad_scale: float = 1.0,
+    norm_sq: Optional[torch.Tensor] = None,
+    max_norm: float = float("inf"),
+    skip_nonfinite: bool = True,
+    span_elems: int = 0,
+):
+    """``fused_adamw_multi_step`` without master weights: ``params`` are the
+    bf16 weights themselves. Per element ``w = float(p)``, the same AdamW
+    update in fp32, ``p = SR(w_new)`` with the noise of ``(seed, streams[i],
+    steps[i], element index)``. Clipping and the non-finite skip work as in
+    ``fused_adamw_multi_step``."""
+    params = list(params)
+    if not params:
+        return
+    seed = int(seed) & ((1 << 64) - 1)
+    if params[0].is_cuda:
+        hip_ops().multi_tensor_adamw_sr(
+            params,
+            [g.contiguous() for g in grads],
+            list(exp_avgs),
+            list(exp_avg_sqs),
+            [float(x) for x in lrs],
+            [float(x) for x in weight_decays],
+            [int(x) for x in steps],
+            [int(x) for x in streams],
+            beta1,
+            beta2,
+            eps,
+            grad_scale,
+            norm_sq,
+            max_norm,
+            skip_nonfinite,
+            seed,
+            span_elems,
+        )
+        return
+    # CPU reference: the fp32 reference step on float(p), then the rounding
+    ws = [p.detach().float() for p in params]
+    fused_adamw_multi_step(
+        ws, grads, exp_avgs, exp_avg_sqs, None, lrs, weight_decays, steps,
+        beta1, beta2, eps, grad_scale, norm_sq, max_norm, skip_nonfinite,
+    )
+    for p, w, stream, step in zip(params, ws, streams, steps):
+        p.copy_(stochastic_round_bf16(w, seed, stream, step))
+
+
+def fused_adamw_fp8_sr_multi_step(
+    params,
+    grads,
+    exp_avgs,
+    exp_avg_scales,
+    exp_avg_sq_roots,
+    exp_avg_sq_root_scales,
+    lrs,
+    weight_decays,
+    steps,
+    streams,
+    beta1: float,
+    beta2: float,
+    eps: float,
+    seed: int,
+    grad_scale: float = 1.0,
+    norm_sq: Optional[torch.Tensor] = None,
+    max_norm: float = float("inf"),
+    skip_nonfinite: bool = True,
+    span_elems: int = 0,
+):
+    """``fused_adamw_sr_multi_step`` on the FP8 block-scaled moments of
+    ``fused_adamw_fp8_multi_step``. Every weight's last dim must be a multiple
+    of 256."""
+    params = list(params)
+    if not params:
+        return
+    seed = int(seed) & ((1 << 64) - 1)
+    if params[0].is_cuda:
+        hip_ops().multi_tensor_adamw_fp8_sr(
+            params,
+            [g.contiguous() for g in grads],
+            list(exp_avgs),
+            list(exp_avg_scales),
+            list(exp_avg_sq_roots),
+            list(exp_avg_sq_root_scales),
+            [float(x) for x in lrs],
+            [float(x) for x in weight_decays],
+            [int(x) for x in steps],
+            [int(x) for x in streams],
+            beta1,
+            beta2,
+            eps,
+            grad_scale,
+            norm_sq,
+            max_norm,
+            skip_nonfinite,
+            seed,
+            span_elems,
+        )
+        return
+    ws = [p.detach().float() for p in params]
+    fused_adamw_fp8_multi_step(
+        ws, grads, exp_avgs, exp_avg_scales, exp_avg_sq_roots,
+        exp_avg_sq_root_scales, None, lrs, weight_decays, steps,
+        beta1, beta2, eps, grad_scale, norm_sq, max_norm, skip_nonfinite,
+    )
+    for p, w, stream, step in zip(params, ws, streams, steps):
+        p.copy_(stochastic_round_bf16(w, seed, stream, step))
+
+
+# ---------------------------------------------------------------------------
 # checkpoint integrity: per-tensor checksums, fused pack / unpack
 # ---------------------------------------------------------------------------
 

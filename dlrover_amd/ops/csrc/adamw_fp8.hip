@@ -18,21 +18,8 @@
 // The conversions are the gfx950 OCP FP8 instructions (v_cvt_pk_fp8_f32 /
 // v_cvt_f32_fp8); tests/test_adamw_fp8_gpu.py compares them exhaustively and
 // bitwise with torch's float8_e4m3fn cast.
-#include "kern_common.h"
+#include "adamw_common.h"
 #include "mt_launch.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define F8_BLOCK 256
-#define F8_E4M3_MAX 448.f
-#define F8_MIN_SCALE 1.17549435e-38f  // FLT_MIN, the smallest normal fp32
-// entries are 88 bytes (two more pointers than MTTensor), so fewer of them
-// fit the kernel-argument segment
-#define F8_MAX_TENSORS 24
-#define F8_MAX_BLOCKS 1024
-#define F8_THREADS 512
-#define F8_WAVES (F8_THREADS / WAVE_SIZE)
-#define F8_FLAG_UNALIGNED 1  // gradient or bf16 weight: scalar accesses
 
 struct F8Tensor {
   float* master;
@@ -58,58 +45,6 @@ struct F8Batch {
 
 // kernel-argument limit; leave room for the other (and hidden) arguments
 static_assert(sizeof(F8Batch) <= 4096 - 512, "F8Batch must fit kernel args");
-
-// ---------------------------------------------------------------------------
-// e4m3fn <-> fp32, four at a time (one dword of codes)
-// ---------------------------------------------------------------------------
-
-__device__ __forceinline__ void e4m3x4_decode(unsigned int codes, float out[4]) {
-  out[0] = __builtin_amdgcn_cvt_f32_fp8((int)codes, 0);
-  out[1] = __builtin_amdgcn_cvt_f32_fp8((int)codes, 1);
-  out[2] = __builtin_amdgcn_cvt_f32_fp8((int)codes, 2);
-  out[3] = __builtin_amdgcn_cvt_f32_fp8((int)codes, 3);
-}
-
-__device__ __forceinline__ unsigned int e4m3x4_encode(const float y[4]) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], w, true);
-  return (unsigned int)w;
-}
-
-// Bit pattern of |x|. As unsigned integers these order like the values they
-// encode, with every NaN above inf: an integer maximum is an absmax that
-// propagates NaN (fmaxf would drop it), like torch.amax.
-__device__ __forceinline__ unsigned int abs_bits(float x) {
-  return __float_as_uint(x) & 0x7fffffffu;
-}
-
-__device__ __forceinline__ unsigned int umax(unsigned int a, unsigned int b) {
-  return a > b ? a : b;
-}
-
-// Quantises the wave's block: x holds this lane's four values, the block
-// scale is returned (identical in every lane).
-__device__ __forceinline__ unsigned int f8_quantize_block(const float x[4],
-                                                          float& scale) {
-  unsigned int bits = umax(umax(abs_bits(x[0]), abs_bits(x[1])),
-                           umax(abs_bits(x[2]), abs_bits(x[3])));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    bits = umax(bits, (unsigned int)__shfl_xor((int)bits, off, WAVE_SIZE));
-  scale = __uint_as_float(bits) / F8_E4M3_MAX;
-  // A scale below the smallest normal fp32 has too few bits to keep x / scale
-  // within +-448 (and may round to 0): such a block, the all-zero one
-  // included, is flushed — scale 0, codes 0, nothing is divided. A NaN scale
-  // is not below anything and goes on to poison its block.
-  if (scale < F8_MIN_SCALE) {
-    scale = 0.f;
-    return 0u;
-  }
-  float y[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) y[j] = x[j] / scale;
-  return e4m3x4_encode(y);
-}
 
 // ---------------------------------------------------------------------------
 // stand-alone quantise / dequantise
@@ -158,15 +93,10 @@ template <bool GRAD_BF16>
 __global__ __launch_bounds__(F8_THREADS) void f8_adamw_kernel(
     const F8Batch b, float beta1, float beta2, float eps, float grad_scale,
     const float* __restrict__ norm_sq, float max_norm, int skip_nonfinite) {
-  float coef = 1.f;
-  if (norm_sq) {
-    const float nsq = norm_sq[0];
-    // inf or NaN norm: leave master, moments and bf16 weights untouched
-    if (skip_nonfinite && !(fabsf(nsq) <= 3.402823466e+38f)) return;
-    const float c = max_norm / (sqrtf(nsq) + 1e-6f);
-    coef = (c > 1.f) ? 1.f : c;  // a NaN propagates, like torch.clamp
-  }
-  const float gs = grad_scale * coef;
+  // inf or NaN norm: leave master, moments and bf16 weights untouched
+  float gs;
+  if (!adamw_grad_scale(norm_sq, max_norm, skip_nonfinite, grad_scale, gs))
+    return;
 
   const F8Tensor& e = b.t[mt_block_entry(b.block_tensor)];
   const long long start = ((long long)blockIdx.x + e.span_bias) * b.span;

@@ -62,6 +62,20 @@ void f8_adamw_launch(int, void* const*, const void* const*, void* const*,
                      const long long*, const float*, const float*, const int*,
                      int, float, float, float, float, const float*, float,
                      int, long long, void*);
+int sr_max_tensors();
+void sr_round_launch(const float*, void*, long long, unsigned long long,
+                     unsigned int, unsigned int, void*);
+void sr_adamw_launch(int, void* const*, const void* const*, void* const*,
+                     void* const*, const long long*, const float*,
+                     const float*, const int*, const int*, int, float, float,
+                     float, float, const float*, float, int,
+                     unsigned long long, long long, void*);
+void sr_f8_adamw_launch(int, void* const*, const void* const*, void* const*,
+                        void* const*, void* const*, void* const*,
+                        const long long*, const float*, const float*,
+                        const int*, const int*, int, float, float, float,
+                        float, const float*, float, int, unsigned long long,
+                        long long, void*);
 int ckpt_span_quantum();
 int ckpt_max_blocks();
 long long ckpt_auto_span(long long);
@@ -861,6 +875,172 @@ void multi_tensor_adamw_fp8(
                   (float)max_norm, skip_nonfinite ? 1 : 0, span, cur_stream());
 }
 
+// ---- master-free AdamW with stochastic rounding (adamw_sr.hip) ------------
+void sr_round(const at::Tensor& x, at::Tensor& out, uint64_t seed,
+              int64_t stream, int64_t step) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat &&
+                  x.is_contiguous(),
+              "sr_round: x must be contiguous fp32 on GPU");
+  TORCH_CHECK(out.is_cuda() && out.device() == x.device() &&
+                  out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+                  out.numel() == x.numel(),
+              "sr_round: out must be contiguous bf16 on x's device, numel "
+              "matching");
+  TORCH_CHECK(stream >= 0 && stream < (1LL << 32) && step >= 0 &&
+                  step < (1LL << 32),
+              "sr_round: stream and step must fit 32 bits");
+  if (x.numel() == 0) return;
+  sr_round_launch((const float*)x.data_ptr(), out.data_ptr(),
+                  (long long)x.numel(), seed, (unsigned int)stream,
+                  (unsigned int)step, cur_stream());
+}
+
+// per-tensor scalars and the clip norm, shared by the two updates below
+struct SrArgs {
+  std::vector<float> lr, wd;
+  std::vector<int> step, stream;
+  const float* nsq = nullptr;
+};
+
+SrArgs sr_args(size_t n, const std::vector<double>& lrs,
+               const std::vector<double>& weight_decays,
+               const std::vector<int64_t>& steps,
+               const std::vector<int64_t>& streams,
+               const c10::optional<at::Tensor>& norm_sq) {
+  TORCH_CHECK(lrs.size() == n && weight_decays.size() == n &&
+                  steps.size() == n && streams.size() == n,
+              "adamw_sr: list lengths differ");
+  SrArgs a;
+  a.lr.resize(n);
+  a.wd.resize(n);
+  a.step.resize(n);
+  a.stream.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    TORCH_CHECK(steps[i] >= 1 && steps[i] < (1LL << 31) && streams[i] >= 0 &&
+                    streams[i] < (1LL << 31),
+                "adamw_sr: steps must be >= 1, streams >= 0, both below 2^31");
+    a.lr[i] = (float)lrs[i];
+    a.wd[i] = (float)weight_decays[i];
+    a.step[i] = (int)steps[i];
+    a.stream[i] = (int)streams[i];
+  }
+  if (norm_sq.has_value()) {
+    TORCH_CHECK(norm_sq->is_cuda() && norm_sq->scalar_type() == at::kFloat &&
+                    norm_sq->numel() >= 1,
+                "norm_sq must be fp32 on GPU");
+    a.nsq = (const float*)norm_sq->data_ptr();
+  }
+  return a;
+}
+
+// one bf16 weight and its gradient
+void check_sr_pair(const at::Tensor& p, const at::Tensor& g, bool gbf16) {
+  check_bf16(p, "param");
+  TORCH_CHECK(g.is_cuda() && g.is_contiguous(), "grad must be GPU");
+  TORCH_CHECK(g.numel() == p.numel(), "grad/param numel mismatch");
+  TORCH_CHECK(g.scalar_type() == (gbf16 ? at::kBFloat16 : at::kFloat),
+              "grads of one call must all be bf16 or all be fp32");
+}
+
+void multi_tensor_adamw_sr(
+    const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+    const std::vector<at::Tensor>& exp_avgs,
+    const std::vector<at::Tensor>& exp_avg_sqs, const std::vector<double>& lrs,
+    const std::vector<double>& weight_decays, const std::vector<int64_t>& steps,
+    const std::vector<int64_t>& streams, double beta1, double beta2, double eps,
+    double grad_scale, c10::optional<at::Tensor> norm_sq, double max_norm,
+    bool skip_nonfinite, uint64_t seed, int64_t span_elems) {
+  const size_t n = params.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n &&
+                  exp_avg_sqs.size() == n,
+              "multi_tensor_adamw_sr: list lengths differ");
+  if (n == 0) return;
+  const SrArgs a = sr_args(n, lrs, weight_decays, steps, streams, norm_sq);
+  const auto numel = mt_numels(params);
+  const long long span = mt_span(numel, span_elems);
+  const bool gbf16 = grads[0].scalar_type() == at::kBFloat16;
+  std::vector<void*> pp(n), pe(n), pv(n);
+  std::vector<const void*> pg(n);
+  for (size_t i = 0; i < n; ++i) {
+    const auto& p = params[i];
+    check_sr_pair(p, grads[i], gbf16);
+    for (const at::Tensor* t : {&exp_avgs[i], &exp_avg_sqs[i]})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                      t->is_contiguous() && t->numel() == p.numel(),
+                  "moments must be contiguous fp32 on GPU, numel matching");
+    pp[i] = p.data_ptr();
+    pg[i] = grads[i].data_ptr();
+    pe[i] = exp_avgs[i].data_ptr();
+    pv[i] = exp_avg_sqs[i].data_ptr();
+  }
+  TORCH_CHECK(mt_num_blocks((int)n, numel.data(), span) < (1LL << 31),
+              "multi_tensor_adamw_sr: too many spans");
+  sr_adamw_launch((int)n, pp.data(), pg.data(), pe.data(), pv.data(),
+                  numel.data(), a.lr.data(), a.wd.data(), a.step.data(),
+                  a.stream.data(), gbf16 ? 1 : 0, (float)beta1, (float)beta2,
+                  (float)eps, (float)grad_scale, a.nsq, (float)max_norm,
+                  skip_nonfinite ? 1 : 0, seed, span, cur_stream());
+}
+
+void multi_tensor_adamw_fp8_sr(
+    const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+    const std::vector<at::Tensor>& exp_avgs,
+    const std::vector<at::Tensor>& exp_avg_scales,
+    const std::vector<at::Tensor>& exp_avg_sq_roots,
+    const std::vector<at::Tensor>& exp_avg_sq_root_scales,
+    const std::vector<double>& lrs, const std::vector<double>& weight_decays,
+    const std::vector<int64_t>& steps, const std::vector<int64_t>& streams,
+    double beta1, double beta2, double eps, double grad_scale,
+    c10::optional<at::Tensor> norm_sq, double max_norm, bool skip_nonfinite,
+    uint64_t seed, int64_t span_elems) {
+  const size_t n = params.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n &&
+                  exp_avg_scales.size() == n && exp_avg_sq_roots.size() == n &&
+                  exp_avg_sq_root_scales.size() == n,
+              "multi_tensor_adamw_fp8_sr: list lengths differ");
+  if (n == 0) return;
+  const SrArgs a = sr_args(n, lrs, weight_decays, steps, streams, norm_sq);
+  const int64_t block = f8_block_elems();
+  TORCH_CHECK(span_elems >= 0 && span_elems % block == 0 &&
+                  span_elems < (1LL << 31),
+              "span_elems must be 0 (automatic) or a positive multiple of ",
+              block, " below 2^31");
+  const auto numel = mt_numels(params);
+  long long span = span_elems;
+  if (span == 0) {
+    long long total = 0;
+    for (long long k : numel) total += k;
+    span = f8_auto_span(total);
+  }
+  const bool gbf16 = grads[0].scalar_type() == at::kBFloat16;
+  std::vector<void*> pp(n), pe(n), pes(n), pr(n), prs(n);
+  std::vector<const void*> pg(n);
+  for (size_t i = 0; i < n; ++i) {
+    const auto& p = params[i];
+    check_sr_pair(p, grads[i], gbf16);
+    check_f8_pair(exp_avgs[i], exp_avg_scales[i], "exp_avg");
+    check_f8_pair(exp_avg_sq_roots[i], exp_avg_sq_root_scales[i],
+                  "exp_avg_sq_root");
+    TORCH_CHECK(exp_avgs[i].sizes() == p.sizes() &&
+                    exp_avg_sq_roots[i].sizes() == p.sizes(),
+                "moment codes must have the param's shape");
+    pp[i] = p.data_ptr();
+    pg[i] = grads[i].data_ptr();
+    pe[i] = exp_avgs[i].data_ptr();
+    pes[i] = exp_avg_scales[i].data_ptr();
+    pr[i] = exp_avg_sq_roots[i].data_ptr();
+    prs[i] = exp_avg_sq_root_scales[i].data_ptr();
+  }
+  TORCH_CHECK(mt_num_blocks((int)n, numel.data(), span) < (1LL << 31),
+              "multi_tensor_adamw_fp8_sr: too many spans");
+  sr_f8_adamw_launch((int)n, pp.data(), pg.data(), pe.data(), pes.data(),
+                     pr.data(), prs.data(), numel.data(), a.lr.data(),
+                     a.wd.data(), a.step.data(), a.stream.data(),
+                     gbf16 ? 1 : 0, (float)beta1, (float)beta2, (float)eps,
+                     (float)grad_scale, a.nsq, (float)max_norm,
+                     skip_nonfinite ? 1 : 0, seed, span, cur_stream());
+}
+
 // ---- FP8 tensor-wise cast for the linear layers (fp8_cast.hip) -----------
 // x: [R, C] bf16 or fp32, contiguous, 16-byte aligned, R and C multiples of 16
 bool check_fp8_cast_input(const at::Tensor& x, const char* op) {
@@ -1109,6 +1289,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
         py::arg("grad_scale"), py::arg("norm_sq"), py::arg("max_norm"),
         py::arg("skip_nonfinite"), py::arg("span_elems") = 0);
+  m.attr("SR_MAX_TENSORS") = sr_max_tensors();
+  m.def("sr_round", &sr_round,
+        "out = stochastic rounding of fp32 x to bf16, Philox4x32-10 noise "
+        "keyed on (seed, stream, step, element index)",
+        py::arg("x"), py::arg("out"), py::arg("seed"), py::arg("stream"),
+        py::arg("step"));
+  m.def("multi_tensor_adamw_sr", &multi_tensor_adamw_sr,
+        "batched fused AdamW on bf16 weights without an fp32 master: the "
+        "update is computed in fp32 and rounded stochastically",
+        py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_sqs"), py::arg("lrs"), py::arg("weight_decays"),
+        py::arg("steps"), py::arg("streams"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("grad_scale"),
+        py::arg("norm_sq"), py::arg("max_norm"), py::arg("skip_nonfinite"),
+        py::arg("seed"), py::arg("span_elems") = 0);
+  m.def("multi_tensor_adamw_fp8_sr", &multi_tensor_adamw_fp8_sr,
+        "multi_tensor_adamw_sr on FP8 block-scaled moments",
+        py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_scales"), py::arg("exp_avg_sq_roots"),
+        py::arg("exp_avg_sq_root_scales"), py::arg("lrs"),
+        py::arg("weight_decays"), py::arg("steps"), py::arg("streams"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("grad_scale"), py::arg("norm_sq"), py::arg("max_norm"),
+        py::arg("skip_nonfinite"), py::arg("seed"),
+        py::arg("span_elems") = 0);
   m.attr("CKPT_SPAN_QUANTUM") = ckpt_span_quantum();
   m.attr("CKPT_MAX_BLOCKS") = ckpt_max_blocks();
   m.def("fp8_amax_slots", &fp8_amax_slots,

@@ -16,10 +16,8 @@
 // partial into its own slot and a single-block finalize adds the slots in a
 // fixed order (fp64), so the norm — and with it every clipped update — is
 // bitwise reproducible from run to run.
-#include "kern_common.h"
+#include "adamw_common.h"
 #include "mt_launch.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define MT_MAX_TENSORS 32
 #define MT_MAX_BLOCKS 1024
@@ -155,15 +153,10 @@ template <bool GRAD_BF16>
 __global__ __launch_bounds__(MT_THREADS) void mt_adamw_kernel(
     const MTBatch b, float beta1, float beta2, float eps, float grad_scale,
     const float* __restrict__ norm_sq, float max_norm, int skip_nonfinite) {
-  float coef = 1.f;
-  if (norm_sq) {
-    const float nsq = norm_sq[0];
-    // inf or NaN norm: leave master, moments and bf16 weights untouched
-    if (skip_nonfinite && !(fabsf(nsq) <= 3.402823466e+38f)) return;
-    const float c = max_norm / (sqrtf(nsq) + 1e-6f);
-    coef = (c > 1.f) ? 1.f : c;  // a NaN propagates, like torch.clamp
-  }
-  const float gs = grad_scale * coef;
+  // inf or NaN norm: leave master, moments and bf16 weights untouched
+  float gs;
+  if (!adamw_grad_scale(norm_sq, max_norm, skip_nonfinite, grad_scale, gs))
+    return;
 
   const MTTensor& e = b.t[mt_block_tensor(b)];
   const long long start = ((long long)blockIdx.x + e.span_bias) * b.span;
@@ -248,10 +241,6 @@ __global__ __launch_bounds__(MT_THREADS) void mt_adamw_kernel(
 // ---------------------------------------------------------------------------
 
 namespace {
-
-inline bool misaligned16(const void* p) {
-  return p != nullptr && ((uintptr_t)p & 15u) != 0;
-}
 
 // fill(i, entry) sets everything but numel and span_bias; launch(batch,
 // n_blocks) fires one kernel. Zero-numel tensors are skipped. The cutting

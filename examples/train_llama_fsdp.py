@@ -44,6 +44,12 @@ def main():
                    help="fp8: keep the Adam moments of every weight whose "
                         "last dim is a multiple of 256 as e4m3 codes with "
                         "per-256-element scales (half the checkpointed state)")
+    p.add_argument("--no-master-weights", action="store_true",
+                   help="keep no fp32 master copy of the bf16 weights: update "
+                        "them with stochastic rounding (4 bytes per parameter "
+                        "less state; a resumed run needs the same --sr-seed)")
+    p.add_argument("--sr-seed", type=int, default=0,
+                   help="seed of the stochastic-rounding noise")
     p.add_argument("--linear", choices=("bf16", "fp8"), default="bf16",
                    help="fp8: the qkv, o, gate_up and down projections run "
                         "their GEMMs on FP8 operands (e4m3 activations and "
@@ -104,7 +110,9 @@ def main():
         fully_shard(model)
     clip_kw = {"max_grad_norm": args.grad_clip} if args.grad_clip > 0 else {}
     opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=0.1,
-                     moments=args.optim_moments, **clip_kw)
+                     moments=args.optim_moments,
+                     master_weights=not args.no_master_weights,
+                     sr_seed=args.sr_seed, **clip_kw)
     trainer = ElasticTrainer(model)
 
     cp = FsdpShardCheckpointer(
