@@ -20,6 +20,7 @@ import torch.nn as nn
 from dlrover_amd.ops import (
     causal_softmax,
     cross_entropy_loss,
+    qk_norm_rope,
     rmsnorm,
     rmsnorm_add,
     rope_rotate,
@@ -60,6 +61,12 @@ class LlamaConfig:
     # with one current absmax scale per tensor. lm_head and embed stay as
     # they are. Opt-in; README "The hot path" has the measurements
     linear_precision: str = "bf16"
+    # Qwen3 / OLMo-2 / Gemma-3 attention: an RMSNorm over each head's head_dim
+    # vector of q and of k (one learned weight per head_dim each:
+    # attn.q_norm.weight, attn.k_norm.weight) before RoPE, both fused into
+    # ops.qk_norm_rope. head_dim 64 or 128 on the GPU; not under tensor
+    # parallelism
+    qk_norm: bool = False
 
     def __post_init__(self):
         if self.linear_precision not in ("bf16", "fp8"):
@@ -115,6 +122,23 @@ class LlamaConfig:
         )
 
     @classmethod
+    def qwen3_8b(cls, max_seq_len: int = 8192) -> "LlamaConfig":
+        """Qwen3-8B geometry: Llama architecture + per-head QK-norm."""
+        return cls(
+            vocab_size=151936,
+            hidden_size=4096,
+            intermediate_size=12288,
+            n_layers=36,
+            n_heads=32,
+            n_kv_heads=8,
+            max_seq_len=max_seq_len,
+            rope_base=1000000.0,
+            norm_eps=1e-6,
+            attn_bias=False,
+            qk_norm=True,
+        )
+
+    @classmethod
     def small_1b(cls, max_seq_len: int = 4096) -> "LlamaConfig":
         return cls(
             vocab_size=32000,
@@ -155,6 +179,9 @@ class Attention(nn.Module):
             d, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd, bias=cfg.attn_bias
         )
         self.o_proj = linear(cfg.n_heads * hd, d, bias=False)
+        if cfg.qk_norm:
+            self.q_norm = RMSNorm(hd, cfg.norm_eps)
+            self.k_norm = RMSNorm(hd, cfg.norm_eps)
 
     def forward(self, x, pos, cos, sin, doc_start=None):
         """doc_start [B,S] int32 (optional): packed-sequence document mask —
@@ -167,8 +194,12 @@ class Attention(nn.Module):
         q = q.view(B, S, nh, hd)
         k = k.view(B, S, nkv, hd)
         v = v.view(B, S, nkv, hd)
-        q = rope_rotate(q, pos, cos, sin)
-        k = rope_rotate(k, pos, cos, sin)
+        if cfg.qk_norm:
+            q, k = qk_norm_rope(q, k, self.q_norm.weight, self.k_norm.weight,
+                                pos, cos, sin, cfg.norm_eps)
+        else:
+            q = rope_rotate(q, pos, cos, sin)
+            k = rope_rotate(k, pos, cos, sin)
         use_flash = (
             cfg.attn_impl in ("auto", "flash")
             and x.is_cuda

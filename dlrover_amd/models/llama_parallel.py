@@ -42,6 +42,13 @@ class ParallelAttention(nn.Module):
         tp = groups.dims.tp
         if cfg.n_heads % tp or cfg.n_kv_heads % tp:
             raise ValueError("n_heads and n_kv_heads must divide tp")
+        if cfg.qk_norm:
+            raise ValueError(
+                "qk_norm=True is not supported under tensor parallelism: "
+                "every TP rank sees different heads, so the replicated "
+                "q_norm/k_norm weights would need a gradient all-reduce, "
+                "which is out of scope here; use the single-rank Attention"
+            )
         self.cfg = cfg
         self.groups = groups
         self.nh = cfg.n_heads // tp

@@ -40,6 +40,8 @@ from dlrover_amd.ops.api import (  # noqa: F401
     hip_ops,
     hip_ops_available,
     philox4x32_10,
+    qk_norm_rope,
+    qk_norm_rope_ref,
     rmsnorm,
     rmsnorm_add,
     rope_ref,

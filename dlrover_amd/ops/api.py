@@ -261,6 +261,90 @@ def rope_rotate(
     return _RoPE.apply(x, pos, cos, sin)
 
 
+def qk_norm_rope_ref(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    wq: torch.Tensor,
+    wk: torch.Tensor,
+    pos: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    eps: float = 1e-6,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 composite reference of ``qk_norm_rope``: ``rmsnorm_ref`` over each
+    head vector, then ``rope_ref``, kept in fp32 with one cast at the end."""
+
+    def one(x, w):
+        xf = x.float()
+        inv = torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+        return rope_ref(xf * inv * w.float(), pos, cos, sin).to(x.dtype)
+
+    return one(q, wq), one(k, wk)
+
+
+def _qk_addressable(x: torch.Tensor) -> torch.Tensor:
+    """``_rope_addressable``, and a contiguous tensor gets the canonical
+    strides: torch leaves any stride on a size-1 dim (the k gradient of a
+    one-kv-head attention), which the kernel's token stride is read from."""
+    x = _rope_addressable(x)
+    return x.reshape(-1).view(x.shape) if x.is_contiguous() else x
+
+
+class _QKNormRoPE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, wq, wk, pos, cos, sin, eps):
+        ctx.use_hip = _use_hip(q, k)
+        if ctx.use_hip:
+            # the kernel reads the strided views (the q/k slices of the fused
+            # QKV projection) in place, and backward reads them again: saving
+            # them keeps alive only storage that attention's V already holds
+            q, k = _qk_addressable(q), _qk_addressable(k)
+            pos = pos.int().contiguous()
+            wq, wk = wq.contiguous(), wk.contiguous()
+            q_out, k_out, inv = hip_ops().qk_norm_rope_fwd(
+                q, k, wq, wk, pos, cos, sin, eps
+            )
+            ctx.save_for_backward(q, k, inv, wq, wk, pos, cos, sin)
+            return q_out, k_out
+        leaves = [t.detach().clone().requires_grad_(True)
+                  for t in (q, k, wq, wk)]
+        with torch.enable_grad():
+            outs = qk_norm_rope_ref(*leaves, pos, cos, sin, eps)
+        ctx.saved_ref = (leaves, outs)
+        return outs[0].detach(), outs[1].detach()
+
+    @staticmethod
+    def backward(ctx, dq, dk):
+        if ctx.use_hip:
+            q, k, inv, wq, wk, pos, cos, sin = ctx.saved_tensors
+            dxq, dxk, dwq, dwk = hip_ops().qk_norm_rope_bwd(
+                _qk_addressable(dq), _qk_addressable(dk), q, k, inv, wq, wk,
+                pos, cos, sin
+            )
+            return dxq, dxk, dwq, dwk, None, None, None, None
+        leaves, outs = ctx.saved_ref
+        torch.autograd.backward(outs, (dq, dk))
+        return (*(t.grad for t in leaves), None, None, None, None)
+
+
+def qk_norm_rope(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    wq: torch.Tensor,
+    wk: torch.Tensor,
+    pos: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    eps: float = 1e-6,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """QK-norm attention prologue (Qwen3, OLMo-2, Gemma-3): RMSNorm over each
+    head's head_dim vector of q and of k (weights wq, wk [head_dim]), then
+    rotate-half RoPE. q [..., T, nh, D], k [..., T, nkv, D]; pos, cos, sin as
+    for ``rope_rotate``. On the GPU one HIP launch serves q and k in each
+    direction (ops/csrc/qk_norm_rope.hip): bf16, head_dim 64 or 128."""
+    return _QKNormRoPE.apply(q, k, wq, wk, pos, cos, sin, eps)
+
+
 def build_rope_cache(
     max_pos: int, head_dim: int, base: float = 500000.0, device="cpu"
 ) -> Tuple[torch.Tensor, torch.Tensor]:

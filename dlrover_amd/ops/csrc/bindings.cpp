@@ -25,6 +25,17 @@ void rope_launch(void*, const void*, const void*, const void*, long long,
 void rope_oop_launch(const void*, void*, const void*, const void*,
                      const void*, long long, long long, int, int, long long,
                      int, void*);
+int qk_norm_rope_bwd_slices(long long, int);
+void qk_norm_rope_fwd_launch(const void*, const void*, long long, long long,
+                             const void*, const void*, const void*,
+                             const void*, const void*, void*, void*, void*,
+                             int, int, int, int, int, float, void*);
+void qk_norm_rope_bwd_launch(const void*, const void*, long long, long long,
+                             const void*, const void*, long long, long long,
+                             const void*, const void*, const void*,
+                             const void*, const void*, const void*, void*,
+                             void*, void*, void*, void*, int, int, int, int,
+                             int, void*);
 void swiglu_fwd_launch(const void*, void*, long long, int, void*);
 void swiglu_bwd_launch(const void*, const void*, void*, long long, int, void*);
 void adamw_launch(void*, const void*, void*, void*, void*, long long, float,
@@ -212,6 +223,131 @@ at::Tensor rope_rotate_oop(const at::Tensor& x, const at::Tensor& pos,
                   (long long)pos.numel(), n_heads, head_dim, tok_stride,
                   backward ? 1 : 0, cur_stream());
   return out;
+}
+
+// Token stride of a [..., tokens, heads, D] bf16 view that the QK-norm
+// kernels can address in place: heads*D contiguous inside a token and every
+// leading dim uniformly strided (rope_rotate_oop's rule).
+long long qknr_tok_stride(const at::Tensor& x, const char* name) {
+  TORCH_CHECK(x.is_cuda(), "qk_norm_rope: ", name, " must be on GPU");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "qk_norm_rope: ", name,
+              " must be bf16");
+  TORCH_CHECK(x.dim() >= 3, "qk_norm_rope: ", name,
+              " must be [..., tokens, heads, head_dim]");
+  // the stride of a size-1 dim is never used and may hold anything
+  TORCH_CHECK(x.stride(-1) == 1 &&
+                  (x.size(-2) == 1 || x.stride(-2) == x.size(-1)),
+              "qk_norm_rope: ", name,
+              " needs head_dim/heads contiguous within a token row");
+  const long long tok_stride = x.stride(-3);
+  long long rows = x.size(-3);
+  for (int d = (int)x.dim() - 4; d >= 0; --d) {
+    TORCH_CHECK(x.size(d) == 1 || x.stride(d) == rows * tok_stride,
+                "qk_norm_rope: ", name,
+                " leading dims must be uniformly strided");
+    rows *= x.size(d);
+  }
+  TORCH_CHECK(tok_stride % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "qk_norm_rope: ", name, " must be 16-byte aligned per token");
+  return tok_stride;
+}
+
+// Checks shared by forward and backward; returns the token count.
+long long qknr_check(const at::Tensor& q, const at::Tensor& k,
+                     const at::Tensor& wq, const at::Tensor& wk,
+                     const at::Tensor& pos, const at::Tensor& cos,
+                     const at::Tensor& sin) {
+  const long long hd = q.size(-1);
+  TORCH_CHECK(hd == 64 || hd == 128,
+              "qk_norm_rope: head_dim must be 64 or 128, got ", hd);
+  TORCH_CHECK(k.size(-1) == hd && q.dim() == k.dim(),
+              "qk_norm_rope: q and k must share head_dim and rank");
+  const long long n_tokens = q.numel() / (q.size(-2) * hd);
+  TORCH_CHECK(k.numel() / (k.size(-2) * hd) == n_tokens,
+              "qk_norm_rope: q and k must have the same token count");
+  TORCH_CHECK(n_tokens * (q.size(-2) + k.size(-2)) < (1LL << 31),
+              "qk_norm_rope: more than 2^31 head rows");
+  check_bf16(wq, "wq");
+  check_bf16(wk, "wk");
+  TORCH_CHECK(wq.numel() == hd && wk.numel() == hd,
+              "qk_norm_rope: wq and wk must have head_dim elements");
+  TORCH_CHECK(pos.scalar_type() == at::kInt && pos.is_cuda() &&
+                  pos.is_contiguous(),
+              "qk_norm_rope: pos must be contiguous int32 on GPU");
+  TORCH_CHECK(pos.numel() > 0 && n_tokens % pos.numel() == 0,
+              "qk_norm_rope: pos length must equal or divide the token "
+              "count");
+  for (const at::Tensor* tab : {&cos, &sin})
+    TORCH_CHECK(tab->is_cuda() && tab->scalar_type() == at::kFloat &&
+                    tab->is_contiguous() && tab->dim() == 2 &&
+                    tab->size(1) == hd / 2,
+                "qk_norm_rope: cos/sin must be contiguous fp32 "
+                "[max_pos, head_dim/2] on GPU");
+  TORCH_CHECK(cos.size(0) == sin.size(0),
+              "qk_norm_rope: cos and sin must have the same length");
+  return n_tokens;
+}
+
+// q [..., T, nh, D], k [..., T, nkv, D] (strided views are read in place)
+// -> contiguous q_out, k_out and inv [T_total, nh+nkv] fp32 for backward.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> qk_norm_rope_fwd(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& wq,
+    const at::Tensor& wk, const at::Tensor& pos, const at::Tensor& cos,
+    const at::Tensor& sin, double eps) {
+  const long long q_stride = qknr_tok_stride(q, "q");
+  const long long k_stride = qknr_tok_stride(k, "k");
+  const long long n_tokens = qknr_check(q, k, wq, wk, pos, cos, sin);
+  const int nh = (int)q.size(-2), nkv = (int)k.size(-2);
+  auto q_out = at::empty(q.sizes(), q.options());
+  auto k_out = at::empty(k.sizes(), k.options());
+  auto inv = at::empty({n_tokens, nh + nkv}, q.options().dtype(at::kFloat));
+  if (n_tokens > 0)
+    qk_norm_rope_fwd_launch(
+        q.data_ptr(), k.data_ptr(), q_stride, k_stride, wq.data_ptr(),
+        wk.data_ptr(), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+        q_out.data_ptr(), k_out.data_ptr(), inv.data_ptr(), (int)n_tokens,
+        (int)pos.numel(), nh, nkv, (int)q.size(-1), (float)eps, cur_stream());
+  return {q_out, k_out, inv};
+}
+
+// -> contiguous dx_q, dx_k and bf16 dwq, dwk
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> qk_norm_rope_bwd(
+    const at::Tensor& dyq, const at::Tensor& dyk, const at::Tensor& q,
+    const at::Tensor& k, const at::Tensor& inv, const at::Tensor& wq,
+    const at::Tensor& wk, const at::Tensor& pos, const at::Tensor& cos,
+    const at::Tensor& sin) {
+  const long long dyq_stride = qknr_tok_stride(dyq, "dy_q");
+  const long long dyk_stride = qknr_tok_stride(dyk, "dy_k");
+  const long long q_stride = qknr_tok_stride(q, "q");
+  const long long k_stride = qknr_tok_stride(k, "k");
+  const long long n_tokens = qknr_check(q, k, wq, wk, pos, cos, sin);
+  TORCH_CHECK(dyq.sizes() == q.sizes() && dyk.sizes() == k.sizes(),
+              "qk_norm_rope_bwd: dy shapes must match q and k");
+  const int nh = (int)q.size(-2), nkv = (int)k.size(-2);
+  const int hd = (int)q.size(-1);
+  TORCH_CHECK(inv.is_cuda() && inv.scalar_type() == at::kFloat &&
+                  inv.is_contiguous() &&
+                  inv.numel() == n_tokens * (nh + nkv),
+              "qk_norm_rope_bwd: inv must be contiguous fp32 "
+              "[tokens, nh+nkv]");
+  auto dxq = at::empty(q.sizes(), q.options());
+  auto dxk = at::empty(k.sizes(), k.options());
+  auto dwq = at::empty_like(wq);
+  auto dwk = at::empty_like(wk);
+  if (n_tokens == 0) return {dxq, dxk, dwq.zero_(), dwk.zero_()};
+  const int n_slices =
+      qk_norm_rope_bwd_slices(n_tokens * (long long)(nh + nkv), hd);
+  auto partial =
+      at::empty({n_slices, 2, hd}, q.options().dtype(at::kFloat));
+  qk_norm_rope_bwd_launch(
+      dyq.data_ptr(), dyk.data_ptr(), dyq_stride, dyk_stride, q.data_ptr(),
+      k.data_ptr(), q_stride, k_stride, inv.data_ptr(), wq.data_ptr(),
+      wk.data_ptr(), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+      dxq.data_ptr(), dxk.data_ptr(), partial.data_ptr(), dwq.data_ptr(),
+      dwk.data_ptr(), (int)n_tokens, (int)pos.numel(), nh, nkv, hd,
+      cur_stream());
+  return {dxq, dxk, dwq, dwk};
 }
 
 at::Tensor swiglu_fwd(const at::Tensor& gate_up) {
@@ -1204,6 +1340,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_apply", &rope_apply, "in-place RoPE rotate-half (bf16)");
   m.def("rope_rotate_oop", &rope_rotate_oop,
         "out-of-place RoPE: strided source -> contiguous output");
+  m.def("qk_norm_rope_fwd", &qk_norm_rope_fwd,
+        "fused per-head RMSNorm + RoPE of q and k, forward (bf16)");
+  m.def("qk_norm_rope_bwd", &qk_norm_rope_bwd,
+        "fused per-head RMSNorm + RoPE of q and k, backward (bf16)");
   m.def("swiglu_fwd", &swiglu_fwd, "fused SwiGLU forward (bf16)");
   m.def("swiglu_bwd", &swiglu_bwd, "fused SwiGLU backward (bf16)");
   m.def("adamw_step", &adamw_step, "fused AdamW with fp32 master weights");

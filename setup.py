@@ -21,6 +21,7 @@ sources = [
     os.path.join(CSRC, "bindings.cpp"),
     os.path.join(CSRC, "rmsnorm.hip"),
     os.path.join(CSRC, "rope.hip"),
+    os.path.join(CSRC, "qk_norm_rope.hip"),
     os.path.join(CSRC, "swiglu.hip"),
     os.path.join(CSRC, "adamw.hip"),
     os.path.join(CSRC, "multi_tensor.hip"),
