@@ -20,6 +20,12 @@ import torch.nn as nn
 from dlrover_amd.ops import (
     causal_softmax,
     cross_entropy_loss,
+    moe_combine,
+    moe_dispatch,
+    moe_grouped_mm,
+    moe_load_balance_loss,
+    moe_router,
+    moe_sort,
     qk_norm_rope,
     rmsnorm,
     rmsnorm_add,
@@ -67,8 +73,32 @@ class LlamaConfig:
     # ops.qk_norm_rope. head_dim 64 or 128 on the GPU; not under tensor
     # parallelism
     qk_norm: bool = False
+    # Mixture of experts (Mixtral, Qwen3-MoE): n_experts > 0 replaces every
+    # block's MLP with MoEMLP, a softmax router over n_experts SwiGLU experts
+    # of width moe_intermediate_size (None: intermediate_size), each token
+    # going to its n_experts_per_tok largest router logits. moe_norm_topk
+    # renormalises the chosen probabilities to sum to 1. moe_aux_coef scales
+    # the load-balancing loss (mean over layers) added to the training loss.
+    # 2 <= n_experts <= 256, n_experts_per_tok <= min(8, n_experts); bf16
+    # experts only; not under the TP/PP stack. 0 builds the dense model
+    n_experts: int = 0
+    n_experts_per_tok: int = 2
+    moe_intermediate_size: int = None
+    moe_norm_topk: bool = True
+    moe_aux_coef: float = 0.0
 
     def __post_init__(self):
+        if self.n_experts:
+            if not 2 <= self.n_experts <= 256 or not (
+                    1 <= self.n_experts_per_tok <= min(8, self.n_experts)):
+                raise ValueError(
+                    "MoE needs 2 <= n_experts <= 256 and 1 <= "
+                    "n_experts_per_tok <= min(8, n_experts), got "
+                    f"{self.n_experts} and {self.n_experts_per_tok}")
+            if self.linear_precision == "fp8":
+                raise ValueError(
+                    "linear_precision='fp8' with n_experts > 0: there is no "
+                    "FP8 grouped GEMM for the experts; use 'bf16'")
         if self.linear_precision not in ("bf16", "fp8"):
             raise ValueError(
                 "linear_precision must be 'bf16' or 'fp8', got "
@@ -136,6 +166,22 @@ class LlamaConfig:
             norm_eps=1e-6,
             attn_bias=False,
             qk_norm=True,
+        )
+
+    @classmethod
+    def mixtral_8x7b(cls, max_seq_len: int = 8192) -> "LlamaConfig":
+        """Mixtral-8x7B geometry: 8 experts, top-2, renormalised weights."""
+        return cls(
+            vocab_size=32000,
+            hidden_size=4096,
+            intermediate_size=14336,
+            n_layers=32,
+            n_heads=32,
+            n_kv_heads=8,
+            max_seq_len=max_seq_len,
+            rope_base=1000000.0,
+            n_experts=8,
+            n_experts_per_tok=2,
         )
 
     @classmethod
@@ -276,22 +322,58 @@ class MLP(nn.Module):
         return self.down_proj(swiglu(self.gate_up_proj(x)))
 
 
+class MoEMLP(nn.Module):
+    """Top-k routed SwiGLU experts. The expert weights are single parameters
+    in the [E, K, N] layout of torch.nn.functional.grouped_mm (FSDP2 shards
+    them on dim 0 like any other parameter). forward returns (y, aux): aux is
+    this layer's load-balancing loss, a scalar."""
+
+    def __init__(self, cfg: LlamaConfig):
+        super().__init__()
+        self.cfg = cfg
+        h, e = cfg.hidden_size, cfg.n_experts
+        inner = cfg.moe_intermediate_size or cfg.intermediate_size
+        self.router = nn.Linear(h, e, bias=False)
+        self.experts_gate_up = nn.Parameter(torch.empty(e, h, 2 * inner))
+        self.experts_down = nn.Parameter(torch.empty(e, inner, h))
+
+    def forward(self, x):
+        cfg = self.cfg
+        k = cfg.n_experts_per_tok
+        xf = x.reshape(-1, x.shape[-1])
+        topk_idx, topk_w, probs_mean = moe_router(
+            self.router(xf), k, cfg.moe_norm_topk)
+        offs, row_of_slot, slot_of_row = moe_sort(topk_idx, cfg.n_experts)
+        xp = moe_dispatch(xf, slot_of_row, row_of_slot, k)  # [T*k, H]
+        inner = swiglu(moe_grouped_mm(xp, self.experts_gate_up, offs))
+        yp = moe_grouped_mm(inner, self.experts_down, offs)
+        y = moe_combine(yp, topk_w, row_of_slot)
+        aux = moe_load_balance_loss(probs_mean, offs, xf.shape[0], k)
+        return y.view(x.shape), aux
+
+
 class Block(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
         self.attn_norm = RMSNorm(cfg.hidden_size, cfg.norm_eps)
         self.attn = Attention(cfg)
         self.mlp_norm = RMSNorm(cfg.hidden_size, cfg.norm_eps)
-        self.mlp = MLP(cfg)
+        self.moe = cfg.n_experts > 0
+        self.mlp = MoEMLP(cfg) if self.moe else MLP(cfg)
 
     def forward(self, x, pos, cos, sin, resid=None, doc_start=None):
         """Two forms. Plain (resid=None): the classic pre-norm block.
         Residual-stream (resid given): x is the previous sublayer's BRANCH
         output (None on the first block); both residual adds fuse into the
         following RMSNorm kernel; returns (branch, resid). Must be entered
-        through __call__ so FSDP's unshard hooks fire."""
+        through __call__ so FSDP's unshard hooks fire. An MoE block returns
+        its load-balancing loss as one more value: (x, aux) or
+        (branch, resid, aux)."""
         if resid is None:
             x = x + self.attn(self.attn_norm(x), pos, cos, sin, doc_start)
+            if self.moe:
+                y, aux = self.mlp(self.mlp_norm(x))
+                return x + y, aux
             x = x + self.mlp(self.mlp_norm(x))
             return x
         if x is None:
@@ -302,6 +384,9 @@ class Block(nn.Module):
         a = self.attn(normed, pos, cos, sin, doc_start)
         normed, resid = rmsnorm_add(a, resid, self.mlp_norm.weight,
                                     self.mlp_norm.eps)
+        if self.moe:
+            y, aux = self.mlp(normed)
+            return y, resid, aux
         return self.mlp(normed), resid
 
 
@@ -323,7 +408,11 @@ class LlamaForCausalLM(nn.Module):
         std = 0.02 / math.sqrt(2 * cfg.n_layers)
         for blk in self.blocks:
             nn.init.normal_(blk.attn.o_proj.weight, std=std)
-            nn.init.normal_(blk.mlp.down_proj.weight, std=std)
+            if blk.moe:
+                nn.init.normal_(blk.mlp.experts_gate_up, std=0.02)
+                nn.init.normal_(blk.mlp.experts_down, std=std)
+            else:
+                nn.init.normal_(blk.mlp.down_proj.weight, std=std)
 
     def _apply(self, fn, recurse=True):
         # .bfloat16()/.half() must not narrow the RoPE tables: the HIP kernel
@@ -357,6 +446,8 @@ class LlamaForCausalLM(nn.Module):
                                      dtype=torch.int32).contiguous()
             pos = doc_positions(doc_start)  # [B, S]
         x = self.embed(input_ids)
+        moe = self.cfg.n_experts > 0
+        aux = []  # one load-balancing loss per MoE block
         ckpt = (self.cfg.activation_checkpointing and self.training
                 and torch.is_grad_enabled())
         if ckpt:
@@ -367,17 +458,20 @@ class LlamaForCausalLM(nn.Module):
             branch, resid = None, x
             for blk in self.blocks:
                 if ckpt:
-                    branch, resid = checkpoint(
+                    out = checkpoint(
                         lambda b, r, ds, _blk=blk: _blk(
                             b, pos, self.rope_cos, self.rope_sin, resid=r,
                             doc_start=ds),
                         branch, resid, doc_start, use_reentrant=False,
                     )
                 else:
-                    branch, resid = blk(
+                    out = blk(
                         branch, pos, self.rope_cos, self.rope_sin, resid=resid,
                         doc_start=doc_start,
                     )
+                branch, resid = out[0], out[1]
+                if moe:
+                    aux.append(out[2])
             x, _ = rmsnorm_add(branch, resid, self.final_norm.weight,
                                self.final_norm.eps)
         else:
@@ -392,13 +486,19 @@ class LlamaForCausalLM(nn.Module):
                 else:
                     x = blk(x, pos, self.rope_cos, self.rope_sin,
                             doc_start=doc_start)
+                if moe:
+                    x, layer_aux = x
+                    aux.append(layer_aux)
             x = self.final_norm(x)
         logits = self.lm_head(x)
         if labels is None:
             return logits
-        return cross_entropy_loss(
+        loss = cross_entropy_loss(
             logits.view(-1, self.cfg.vocab_size), labels.view(-1)
         )
+        if moe and self.cfg.moe_aux_coef:
+            loss = loss + self.cfg.moe_aux_coef * torch.stack(aux).mean()
+        return loss
 
     def num_params(self) -> int:
         n = sum(p.numel() for p in self.parameters())

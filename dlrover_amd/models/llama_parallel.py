@@ -100,6 +100,12 @@ class ParallelAttention(nn.Module):
 class ParallelMLP(nn.Module):
     def __init__(self, cfg: LlamaConfig, groups: ParallelGroups):
         super().__init__()
+        if cfg.n_experts > 0:
+            raise ValueError(
+                "n_experts > 0 is not supported under the TP/PP stack: the "
+                "experts are neither tensor- nor expert-parallel here; use "
+                "LlamaForCausalLM under FSDP"
+            )
         tp = groups.dims.tp
         self.gate_up_proj = ColumnParallelLinear(
             cfg.hidden_size, 2 * cfg.intermediate_size, tp, groups.tp_group

@@ -39,6 +39,16 @@ from dlrover_amd.ops.api import (  # noqa: F401
     grad_sq_norm,
     hip_ops,
     hip_ops_available,
+    moe_combine,
+    moe_combine_ref,
+    moe_dispatch,
+    moe_dispatch_ref,
+    moe_grouped_mm,
+    moe_load_balance_loss,
+    moe_router,
+    moe_router_ref,
+    moe_sort,
+    moe_sort_ref,
     philox4x32_10,
     qk_norm_rope,
     qk_norm_rope_ref,

@@ -345,6 +345,254 @@ def qk_norm_rope(
     return _QKNormRoPE.apply(q, k, wq, wk, pos, cos, sin, eps)
 
 
+# ---------------------------------------------------------------------------
+# mixture of experts: router, token sort, dispatch, combine (ops/csrc/moe.hip)
+# ---------------------------------------------------------------------------
+
+MOE_MAX_EXPERTS = 256
+MOE_MAX_TOPK = 8
+
+
+def _moe_acc(t: torch.Tensor) -> torch.dtype:
+    # the references compute in fp32, or in fp64 when handed fp64
+    return torch.float64 if t.dtype == torch.float64 else torch.float32
+
+
+def moe_router_ref(
+    logits: torch.Tensor, k: int, norm_topk: bool = True
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Plain-torch ``moe_router``. The k largest *logits* win, equal logits go
+    to the lower expert index, slots come in descending logit order."""
+    lf = logits.to(_moe_acc(logits))
+    order = torch.sort(lf, dim=-1, descending=True, stable=True).indices
+    idx = order[:, :k]
+    p = torch.softmax(lf, dim=-1)
+    w = p.gather(1, idx)
+    if norm_topk:
+        w = w / w.sum(-1, keepdim=True)
+    return idx.int(), w, p.mean(0)
+
+
+def moe_sort_ref(
+    topk_idx: torch.Tensor, num_experts: int
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Plain-torch ``moe_sort``: a stable sort of the slots by expert."""
+    flat = topk_idx.reshape(-1).long()
+    offs = torch.bincount(flat, minlength=num_experts).cumsum(0).int()
+    slot_of_row = torch.sort(flat, stable=True).indices
+    row_of_slot = torch.empty_like(slot_of_row)
+    row_of_slot[slot_of_row] = torch.arange(flat.numel(), device=flat.device)
+    return offs, row_of_slot.int(), slot_of_row.int()
+
+
+def moe_dispatch_ref(
+    x: torch.Tensor, slot_of_row: torch.Tensor, row_of_slot: torch.Tensor,
+    k: int,
+) -> torch.Tensor:
+    return x[(slot_of_row // k).long()]
+
+
+def moe_combine_ref(
+    yp: torch.Tensor, topk_w: torch.Tensor, row_of_slot: torch.Tensor
+) -> torch.Tensor:
+    T, k = topk_w.shape
+    acc = _moe_acc(yp)
+    rows = yp[row_of_slot.long()].view(T, k, -1).to(acc)
+    return (topk_w.to(acc).unsqueeze(-1) * rows).sum(1).to(yp.dtype)
+
+
+def _moe_check_range(what: str, T: int, E: int, k: int) -> None:
+    if not 2 <= E <= MOE_MAX_EXPERTS:
+        raise ValueError(
+            f"{what}: 2 <= num_experts <= {MOE_MAX_EXPERTS}, got {E}")
+    if not 1 <= k <= min(MOE_MAX_TOPK, E):
+        raise ValueError(
+            f"{what}: 1 <= k <= min({MOE_MAX_TOPK}, num_experts), got {k}")
+    if T * k >= 2 ** 31:
+        raise ValueError(f"{what}: T * k must stay below 2^31, got {T * k}")
+
+
+def _moe_check_rows(what: str, name: str, t: torch.Tensor) -> None:
+    if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[1] % 8:
+        raise ValueError(
+            f"{what}: {name} must be bf16 [rows, H] with H % 8 == 0 on the "
+            f"GPU, got {t.dtype} {tuple(t.shape)}")
+
+
+class _MoERouter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, k, norm_topk):
+        logits = logits.contiguous()
+        idx, w, pm = hip_ops().moe_router_fwd(logits, k, norm_topk)
+        ctx.save_for_backward(logits, idx)
+        ctx.norm_topk = norm_topk
+        ctx.mark_non_differentiable(idx)
+        return idx, w, pm
+
+    @staticmethod
+    def backward(ctx, _d_idx, dw, dpm):
+        logits, idx = ctx.saved_tensors
+        dlogits = hip_ops().moe_router_bwd(
+            logits, idx, dw.float().contiguous(), dpm.float().contiguous(),
+            ctx.norm_topk)
+        return dlogits, None, None
+
+
+def moe_router(
+    logits: torch.Tensor, k: int, norm_topk: bool = True
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Top-k softmax router. logits [T, E] (the output of the router linear)
+    -> (topk_idx int32 [T, k], topk_w fp32 [T, k], probs_mean fp32 [E]).
+
+    The k largest logits win, equal logits go to the lower expert, slots come
+    in descending logit order. With p = softmax(logits) in fp32 over all E,
+    topk_w = p[idx], divided by its sum over the k slots when ``norm_topk``
+    (Mixtral; Qwen3-MoE's norm_topk_prob). probs_mean[e] = mean_t p[t, e]
+    feeds ``moe_load_balance_loss``. topk_w and probs_mean carry gradients to
+    the logits; the selection carries none. GPU: bf16 logits,
+    2 <= E <= 256, k <= min(8, E), T * k < 2^31, else ValueError."""
+    if not _use_hip(logits):
+        return moe_router_ref(logits, k, norm_topk)
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2:
+        raise ValueError(
+            "moe_router: logits must be bf16 [T, E] on the GPU, got "
+            f"{logits.dtype} {tuple(logits.shape)}")
+    _moe_check_range("moe_router", logits.shape[0], logits.shape[1], k)
+    return _MoERouter.apply(logits, int(k), bool(norm_topk))
+
+
+def moe_sort(
+    topk_idx: torch.Tensor, num_experts: int, validate: bool = False
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Stable counting sort of the T*k slots (slot s = t*k + j) by expert ->
+    (offs [E], row_of_slot [T*k], slot_of_row [T*k]), all int32. offs are the
+    inclusive cumulative token counts, the ``offs`` of
+    ``torch.nn.functional.grouped_mm``; row_of_slot is each slot's row in the
+    expert-sorted buffer and slot_of_row its inverse. Rows of one expert keep
+    slot order. The counts stay on the device. ``validate=True`` checks the
+    expert ids against num_experts first, which costs a host sync; without it
+    the kernel counts an id out of range as expert num_experts - 1."""
+    if validate and topk_idx.numel() and (
+            int(topk_idx.min()) < 0 or int(topk_idx.max()) >= num_experts):
+        raise ValueError(
+            f"moe_sort: expert ids must be in [0, {num_experts})")
+    if not _use_hip(topk_idx):
+        return moe_sort_ref(topk_idx, num_experts)
+    if topk_idx.dtype != torch.int32 or topk_idx.dim() != 2:
+        raise ValueError("moe_sort: topk_idx must be int32 [T, k]")
+    _moe_check_range("moe_sort", topk_idx.shape[0], num_experts,
+                     topk_idx.shape[1])
+    return hip_ops().moe_sort(topk_idx.contiguous(), num_experts)
+
+
+class _MoEDispatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, slot_of_row, row_of_slot, k):
+        ctx.save_for_backward(row_of_slot)
+        ctx.k = k
+        return hip_ops().moe_dispatch(x.contiguous(), slot_of_row, k)
+
+    @staticmethod
+    def backward(ctx, dxp):
+        (row_of_slot,) = ctx.saved_tensors
+        dx = hip_ops().moe_combine_fwd(
+            dxp.contiguous(), None, row_of_slot, ctx.k)
+        return dx, None, None, None
+
+
+def moe_dispatch(
+    x: torch.Tensor, slot_of_row: torch.Tensor, row_of_slot: torch.Tensor,
+    k: int,
+) -> torch.Tensor:
+    """xp[r] = x[slot_of_row[r] // k]: the tokens [T, H] laid out in expert
+    order [T*k, H], a bit-exact copy. slot_of_row and row_of_slot are the pair
+    ``moe_sort`` returned; the backward sums each token's k rows in fp32 in
+    slot order. GPU: bf16, H % 8 == 0."""
+    if not _use_hip(x):
+        return moe_dispatch_ref(x, slot_of_row, row_of_slot, k)
+    _moe_check_rows("moe_dispatch", "x", x)
+    if not 1 <= k <= MOE_MAX_TOPK or x.shape[0] * k >= 2 ** 31:
+        raise ValueError(
+            f"moe_dispatch: 1 <= k <= {MOE_MAX_TOPK} and T * k < 2^31")
+    return _MoEDispatch.apply(x, slot_of_row.contiguous(),
+                              row_of_slot.contiguous(), int(k))
+
+
+class _MoECombine(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, yp, topk_w, row_of_slot):
+        yp, topk_w = yp.contiguous(), topk_w.contiguous()
+        ctx.save_for_backward(yp, topk_w, row_of_slot)
+        return hip_ops().moe_combine_fwd(yp, topk_w, row_of_slot,
+                                         topk_w.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        yp, topk_w, row_of_slot = ctx.saved_tensors
+        dyp, dw = hip_ops().moe_combine_bwd(
+            dy.contiguous(), yp, topk_w, row_of_slot)
+        return dyp, dw, None
+
+
+def moe_combine(
+    yp: torch.Tensor, topk_w: torch.Tensor, row_of_slot: torch.Tensor
+) -> torch.Tensor:
+    """y[t] = sum_j topk_w[t, j] * yp[row_of_slot[t*k + j]]: every token
+    gathers its own k expert rows, fp32 accumulation in slot order, one
+    rounding. Gradients go to yp and topk_w. GPU: bf16 yp [T*k, H] with
+    H % 8 == 0, fp32 topk_w [T, k]."""
+    if not _use_hip(yp):
+        return moe_combine_ref(yp, topk_w, row_of_slot)
+    _moe_check_rows("moe_combine", "yp", yp)
+    if topk_w.dtype != torch.float32 or topk_w.dim() != 2 or not (
+            1 <= topk_w.shape[1] <= MOE_MAX_TOPK) or (
+            topk_w.numel() != yp.shape[0]) or topk_w.numel() >= 2 ** 31:
+        raise ValueError(
+            "moe_combine: topk_w must be fp32 [T, k] with k <= "
+            f"{MOE_MAX_TOPK} and T * k == yp rows (< 2^31)")
+    return _MoECombine.apply(yp, topk_w, row_of_slot.contiguous())
+
+
+def moe_load_balance_loss(
+    probs_mean: torch.Tensor, offs: torch.Tensor, T: int, k: int
+) -> torch.Tensor:
+    """Switch-style auxiliary loss E * sum_e f_e * probs_mean[e], where
+    f_e = count_e / (T * k) comes from ``moe_sort``'s offs and is a constant:
+    the gradient flows through probs_mean alone. 1.0 at perfect balance."""
+    counts = torch.diff(offs, prepend=offs.new_zeros(1))
+    f = counts.to(probs_mean.dtype) / float(T * k)
+    return probs_mean.numel() * (f.detach() * probs_mean).sum()
+
+
+# per-expert-loop runs of moe_grouped_mm (one host sync each)
+moe_grouped_mm_fallbacks = 0
+_GROUPED_MM_REJECTED = set()  # (device type, dtype) the library turned down
+
+
+def moe_grouped_mm(
+    x: torch.Tensor, w: torch.Tensor, offs: torch.Tensor
+) -> torch.Tensor:
+    """Expert GEMMs: rows [offs[e-1], offs[e]) of x [R, K] times w[e] of
+    w [E, K, N] -> [R, N]. This is the library's
+    ``torch.nn.functional.grouped_mm``; where the build rejects it for a
+    device and dtype, a loop over ``offs.tolist()`` (one host sync) takes its
+    place and ``moe_grouped_mm_fallbacks`` counts each such call."""
+    global moe_grouped_mm_fallbacks
+    key = (x.device.type, x.dtype)
+    grouped_mm = getattr(torch.nn.functional, "grouped_mm", None)
+    if grouped_mm is not None and key not in _GROUPED_MM_REJECTED:
+        try:
+            return grouped_mm(x, w, offs=offs)
+        except (RuntimeError, NotImplementedError):
+            _GROUPED_MM_REJECTED.add(key)
+    moe_grouped_mm_fallbacks += 1
+    outs, start = [], 0
+    for e, end in enumerate(offs.tolist()):
+        outs.append(x[start:end] @ w[e])
+        start = end
+    return torch.cat(outs)
+
+
 def build_rope_cache(
     max_pos: int, head_dim: int, base: float = 500000.0, device="cpu"
 ) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -11,6 +11,7 @@
 
 #include "attention_launch.h"
 #include "fp8_cast_launch.h"
+#include "moe_launch.h"
 
 extern "C" {
 void rmsnorm_fwd_launch(const void*, const void*, void*, void*, int, int,
@@ -1329,6 +1330,169 @@ void ckpt_copy_sum(int64_t mode, const std::vector<at::Tensor>& tensors,
                        (long long*)sums.data_ptr(), cur_stream());
 }
 
+// ---- mixture of experts (moe.hip) ------------------------------------------
+void check_moe_tensor(const at::Tensor& t, at::ScalarType dtype,
+                      const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == dtype,
+              "moe: ", name, " must be a contiguous ", dtype, " GPU tensor");
+}
+
+// bf16 [rows, H] with H % 8 == 0 and 16-byte aligned rows
+void check_moe_rows(const at::Tensor& t, const char* name) {
+  check_moe_tensor(t, at::kBFloat16, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(1) > 0 && t.size(1) % 8 == 0 &&
+                  t.size(1) < (1LL << 31) &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              "moe: ", name, " must be 16-byte aligned [rows, H], H % 8 == 0");
+}
+
+// Validates [T, k] against the supported range; returns T.
+long long check_moe_tk(const at::Tensor& t, int64_t E, const char* name) {
+  TORCH_CHECK(t.dim() == 2, "moe: ", name, " must be [T, k]");
+  const int64_t T = t.size(0), k = t.size(1);
+  TORCH_CHECK(E >= 2 && E <= MOE_MAX_EXPERTS, "moe: 2 <= E <= ",
+              MOE_MAX_EXPERTS, " experts, got ", E);
+  TORCH_CHECK(k >= 1 && k <= MOE_MAX_TOPK && k <= E,
+              "moe: 1 <= k <= min(", MOE_MAX_TOPK, ", E), got ", k);
+  TORCH_CHECK(T * k < (1LL << 31), "moe: T * k must stay below 2^31");
+  return T;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_router_fwd(
+    const at::Tensor& logits, int64_t k, bool norm_topk) {
+  check_moe_tensor(logits, at::kBFloat16, "logits");
+  TORCH_CHECK(logits.dim() == 2, "moe: logits must be [T, E]");
+  const int64_t T = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(k >= 1 && k <= MOE_MAX_TOPK, "moe: 1 <= k <= ", MOE_MAX_TOPK);
+  auto topk_idx = at::empty({T, k}, logits.options().dtype(at::kInt));
+  auto topk_w = at::empty({T, k}, logits.options().dtype(at::kFloat));
+  check_moe_tk(topk_idx, E, "topk_idx");
+  auto probs_mean = at::zeros({E}, logits.options().dtype(at::kFloat));
+  if (T == 0) return {topk_idx, topk_w, probs_mean};
+  auto partials = at::empty({moe_router_num_partials(T), E},
+                            logits.options().dtype(at::kFloat));
+  moe_router_fwd_launch(logits.data_ptr(), (int*)topk_idx.data_ptr(),
+                        (float*)topk_w.data_ptr(),
+                        (float*)probs_mean.data_ptr(),
+                        (float*)partials.data_ptr(), T, (int)E, (int)k,
+                        norm_topk ? 1 : 0, attn_stream());
+  return {topk_idx, topk_w, probs_mean};
+}
+
+at::Tensor moe_router_bwd(const at::Tensor& logits, const at::Tensor& topk_idx,
+                          const at::Tensor& d_topk_w,
+                          const at::Tensor& d_probs_mean, bool norm_topk) {
+  check_moe_tensor(logits, at::kBFloat16, "logits");
+  check_moe_tensor(topk_idx, at::kInt, "topk_idx");
+  check_moe_tensor(d_topk_w, at::kFloat, "d_topk_w");
+  check_moe_tensor(d_probs_mean, at::kFloat, "d_probs_mean");
+  TORCH_CHECK(logits.dim() == 2, "moe: logits must be [T, E]");
+  const int64_t E = logits.size(1);
+  const long long T = check_moe_tk(topk_idx, E, "topk_idx");
+  TORCH_CHECK(logits.size(0) == T && d_topk_w.sizes() == topk_idx.sizes() &&
+                  d_probs_mean.numel() == E,
+              "moe_router_bwd: shapes must be logits [T, E], topk_idx and "
+              "d_topk_w [T, k], d_probs_mean [E]");
+  auto dlogits = at::empty_like(logits);
+  if (T > 0)
+    moe_router_bwd_launch(logits.data_ptr(), (const int*)topk_idx.data_ptr(),
+                          (const float*)d_topk_w.data_ptr(),
+                          (const float*)d_probs_mean.data_ptr(),
+                          dlogits.data_ptr(), T, (int)E,
+                          (int)topk_idx.size(1), norm_topk ? 1 : 0,
+                          attn_stream());
+  return dlogits;
+}
+
+// -> offs [E], row_of_slot [T*k], slot_of_row [T*k], all int32
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_sort(
+    const at::Tensor& topk_idx, int64_t num_experts) {
+  check_moe_tensor(topk_idx, at::kInt, "topk_idx");
+  const long long n_slots =
+      check_moe_tk(topk_idx, num_experts, "topk_idx") * topk_idx.size(1);
+  auto offs = at::zeros({num_experts}, topk_idx.options());
+  auto row_of_slot = at::empty({n_slots}, topk_idx.options());
+  auto slot_of_row = at::empty({n_slots}, topk_idx.options());
+  if (n_slots == 0) return {offs, row_of_slot, slot_of_row};
+  auto hist = at::empty({num_experts, moe_sort_num_blocks(n_slots)},
+                        topk_idx.options());
+  moe_sort_launch((const int*)topk_idx.data_ptr(), (int*)hist.data_ptr(),
+                  (int*)offs.data_ptr(), (int*)row_of_slot.data_ptr(),
+                  (int*)slot_of_row.data_ptr(), n_slots, (int)num_experts,
+                  attn_stream());
+  return {offs, row_of_slot, slot_of_row};
+}
+
+// An index array of T * k slots.
+void check_moe_slots(const at::Tensor& idx, int64_t T, int64_t k,
+                     const char* name) {
+  check_moe_tensor(idx, at::kInt, name);
+  TORCH_CHECK(k >= 1 && k <= MOE_MAX_TOPK, "moe: 1 <= k <= ", MOE_MAX_TOPK);
+  TORCH_CHECK(T * k < (1LL << 31) && idx.numel() == T * k, "moe: ", name,
+              " must hold T * k = ", T * k, " slots (< 2^31), got ",
+              idx.numel());
+}
+
+at::Tensor moe_dispatch(const at::Tensor& x, const at::Tensor& slot_of_row,
+                        int64_t k) {
+  check_moe_rows(x, "x");
+  const int64_t T = x.size(0), H = x.size(1);
+  check_moe_slots(slot_of_row, T, k, "slot_of_row");
+  auto xp = at::empty({T * k, H}, x.options());
+  if (T > 0)
+    moe_dispatch_launch(x.data_ptr(), (const int*)slot_of_row.data_ptr(),
+                        xp.data_ptr(), T, (int)k, (int)H, attn_stream());
+  return xp;
+}
+
+// topk_w absent: unit weights, k given (the dispatch backward)
+at::Tensor moe_combine_fwd(const at::Tensor& yp,
+                           c10::optional<at::Tensor> topk_w,
+                           const at::Tensor& row_of_slot, int64_t k) {
+  check_moe_rows(yp, "yp");
+  const float* w = nullptr;
+  if (topk_w.has_value()) {
+    check_moe_tensor(*topk_w, at::kFloat, "topk_w");
+    TORCH_CHECK(topk_w->dim() == 2 && topk_w->size(1) == k,
+                "moe: topk_w must be [T, k]");
+    w = (const float*)topk_w->data_ptr();
+  }
+  TORCH_CHECK(k >= 1 && yp.size(0) % k == 0, "moe: yp must have T * k rows");
+  const int64_t T = yp.size(0) / k, H = yp.size(1);
+  TORCH_CHECK(!topk_w.has_value() || topk_w->size(0) == T,
+              "moe: topk_w must be [T, k]");
+  check_moe_slots(row_of_slot, T, k, "row_of_slot");
+  auto y = at::empty({T, H}, yp.options());
+  if (T > 0)
+    moe_combine_fwd_launch(yp.data_ptr(), w,
+                           (const int*)row_of_slot.data_ptr(), y.data_ptr(),
+                           T, (int)k, (int)H, attn_stream());
+  return y;
+}
+
+// -> dyp [T*k, H] bf16, d_topk_w [T, k] fp32
+std::tuple<at::Tensor, at::Tensor> moe_combine_bwd(
+    const at::Tensor& dy, const at::Tensor& yp, const at::Tensor& topk_w,
+    const at::Tensor& row_of_slot) {
+  check_moe_rows(dy, "dy");
+  check_moe_rows(yp, "yp");
+  check_moe_tensor(topk_w, at::kFloat, "topk_w");
+  TORCH_CHECK(topk_w.dim() == 2, "moe: topk_w must be [T, k]");
+  const int64_t T = topk_w.size(0), k = topk_w.size(1), H = yp.size(1);
+  check_moe_slots(row_of_slot, T, k, "row_of_slot");
+  TORCH_CHECK(dy.size(0) == T && dy.size(1) == H && yp.size(0) == T * k,
+              "moe_combine_bwd: shapes must be dy [T, H], yp [T*k, H]");
+  auto dyp = at::empty_like(yp);
+  auto dw = at::empty_like(topk_w);
+  if (T > 0)
+    moe_combine_bwd_launch(dy.data_ptr(), yp.data_ptr(),
+                           (const float*)topk_w.data_ptr(),
+                           (const int*)row_of_slot.data_ptr(), dyp.data_ptr(),
+                           (float*)dw.data_ptr(), T, (int)k, (int)H,
+                           attn_stream());
+  return {dyp, dw};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1344,6 +1508,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused per-head RMSNorm + RoPE of q and k, forward (bf16)");
   m.def("qk_norm_rope_bwd", &qk_norm_rope_bwd,
         "fused per-head RMSNorm + RoPE of q and k, backward (bf16)");
+  m.def("moe_router_fwd", &moe_router_fwd,
+        "MoE router: logits [T, E] bf16 -> (topk_idx int32 [T, k], topk_w "
+        "fp32 [T, k], probs_mean fp32 [E]); top-k on the logits, ties to the "
+        "lower expert",
+        py::arg("logits"), py::arg("k"), py::arg("norm_topk"));
+  m.def("moe_router_bwd", &moe_router_bwd, "MoE router backward -> dlogits",
+        py::arg("logits"), py::arg("topk_idx"), py::arg("d_topk_w"),
+        py::arg("d_probs_mean"), py::arg("norm_topk"));
+  m.def("moe_sort", &moe_sort,
+        "stable counting sort of the T*k slots by expert -> (offs [E], "
+        "row_of_slot, slot_of_row), int32, counts stay on the device",
+        py::arg("topk_idx"), py::arg("num_experts"));
+  m.def("moe_dispatch", &moe_dispatch,
+        "xp[r] = x[slot_of_row[r] / k] (bf16 row gather)", py::arg("x"),
+        py::arg("slot_of_row"), py::arg("k"));
+  m.def("moe_combine_fwd", &moe_combine_fwd,
+        "y[t] = sum_j topk_w[t, j] * yp[row_of_slot[t*k+j]]; unit weights "
+        "when topk_w is None",
+        py::arg("yp"), py::arg("topk_w"), py::arg("row_of_slot"),
+        py::arg("k"));
+  m.def("moe_combine_bwd", &moe_combine_bwd,
+        "MoE combine backward -> (dyp bf16 [T*k, H], d_topk_w fp32 [T, k])",
+        py::arg("dy"), py::arg("yp"), py::arg("topk_w"),
+        py::arg("row_of_slot"));
   m.def("swiglu_fwd", &swiglu_fwd, "fused SwiGLU forward (bf16)");
   m.def("swiglu_bwd", &swiglu_bwd, "fused SwiGLU backward (bf16)");
   m.def("adamw_step", &adamw_step, "fused AdamW with fp32 master weights");

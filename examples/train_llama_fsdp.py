@@ -26,7 +26,15 @@ import torch.distributed as dist
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--model", default="llama3_8b",
-                   choices=["llama3_8b", "small_1b", "tiny"])
+                   choices=["llama3_8b", "small_1b", "tiny", "mixtral_8x7b"])
+    p.add_argument("--experts", type=int, default=None,
+                   help="mixture of experts: replace every MLP with this many "
+                        "routed SwiGLU experts (2..256; 0 = dense; default: "
+                        "what --model has)")
+    p.add_argument("--experts-per-tok", type=int, default=None,
+                   help="experts each token is routed to (1..8)")
+    p.add_argument("--moe-aux-coef", type=float, default=0.01,
+                   help="weight of the load-balancing loss of an MoE model")
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--batch", type=int, default=1)
     p.add_argument("--seq", type=int, default=4096)
@@ -93,6 +101,12 @@ def main():
         args.seq = min(args.seq, cfg.max_seq_len)
     cfg = dataclasses.replace(cfg, activation_checkpointing=args.act_ckpt,
                               linear_precision=args.linear)
+    moe_kw = {"moe_aux_coef": args.moe_aux_coef}
+    if args.experts is not None:
+        moe_kw["n_experts"] = args.experts
+    if args.experts_per_tok is not None:
+        moe_kw["n_experts_per_tok"] = args.experts_per_tok
+    cfg = dataclasses.replace(cfg, **moe_kw)
     with device:
         model = LlamaForCausalLM(cfg)
     model = model.to(device)
