@@ -86,8 +86,18 @@ class LlamaConfig:
     moe_intermediate_size: int = None
     moe_norm_topk: bool = True
     moe_aux_coef: float = 0.0
+    # The expert GEMMs. "library": torch.nn.functional.grouped_mm on the rows
+    # moe_dispatch gathered. "hip": ops/csrc/moe_gemm.hip, the project's bf16
+    # MFMA grouped GEMMs with the dispatch fused into the first one, so the
+    # [T*k, H] copy of the tokens is never written or saved; hidden and expert
+    # widths must be multiples of 32 on the GPU. Opt-in; README "The hot path"
+    moe_expert_gemm: str = "library"
 
     def __post_init__(self):
+        if self.moe_expert_gemm not in ("library", "hip"):
+            raise ValueError(
+                "moe_expert_gemm must be 'library' or 'hip', got "
+                f"{self.moe_expert_gemm!r}")
         if self.n_experts:
             if not 2 <= self.n_experts <= 256 or not (
                     1 <= self.n_experts_per_tok <= min(8, self.n_experts)):
@@ -344,9 +354,16 @@ class MoEMLP(nn.Module):
         topk_idx, topk_w, probs_mean = moe_router(
             self.router(xf), k, cfg.moe_norm_topk)
         offs, row_of_slot, slot_of_row = moe_sort(topk_idx, cfg.n_experts)
-        xp = moe_dispatch(xf, slot_of_row, row_of_slot, k)  # [T*k, H]
-        inner = swiglu(moe_grouped_mm(xp, self.experts_gate_up, offs))
-        yp = moe_grouped_mm(inner, self.experts_down, offs)
+        impl = cfg.moe_expert_gemm
+        if impl == "hip":  # the dispatch is fused into the first GEMM
+            gate_up = moe_grouped_mm(
+                xf, self.experts_gate_up, offs, impl=impl,
+                gather=(slot_of_row, row_of_slot, k))
+        else:
+            xp = moe_dispatch(xf, slot_of_row, row_of_slot, k)  # [T*k, H]
+            gate_up = moe_grouped_mm(xp, self.experts_gate_up, offs)
+        inner = swiglu(gate_up)
+        yp = moe_grouped_mm(inner, self.experts_down, offs, impl=impl)
         y = moe_combine(yp, topk_w, row_of_slot)
         aux = moe_load_balance_loss(probs_mean, offs, xf.shape[0], k)
         return y.view(x.shape), aux

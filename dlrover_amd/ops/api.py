@@ -569,15 +569,103 @@ moe_grouped_mm_fallbacks = 0
 _GROUPED_MM_REJECTED = set()  # (device type, dtype) the library turned down
 
 
+class _MoEGroupedMM(torch.autograd.Function):
+    """The three grouped GEMMs of ops/csrc/moe_gemm.hip. With a gather, x is
+    the token tensor [T, K] and only it is saved: no [T*k, K] copy exists."""
+
+    @staticmethod
+    def forward(ctx, x, w, offs, slot_of_row, row_of_slot, k):
+        x, w = x.contiguous(), w.contiguous()
+        ctx.save_for_backward(x, w, offs, slot_of_row, row_of_slot)
+        ctx.k = k
+        return hip_ops().moe_gemm_fwd(x, w, offs, slot_of_row, k)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, offs, slot_of_row, row_of_slot = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = hip_ops().moe_gemm_dgrad(dy, w, offs)
+            if slot_of_row is not None:  # the backward of the dispatch
+                dx = hip_ops().moe_combine_fwd(dx, None, row_of_slot, ctx.k)
+        if ctx.needs_input_grad[1]:
+            dw = hip_ops().moe_gemm_wgrad(x, dy, offs, slot_of_row, ctx.k)
+        return dx, dw, None, None, None, None
+
+
+def _moe_grouped_mm_hip(x, w, offs, gather):
+    slot_of_row = row_of_slot = None
+    k = 1
+    if gather is not None:
+        slot_of_row, row_of_slot, k = gather
+    if not _use_hip(x):  # CPU: the same sums as a plain loop over the experts
+        if gather is not None:
+            x = x[(slot_of_row // k).long()]
+        outs, start = [], 0
+        for e, end in enumerate(offs.tolist()):
+            outs.append(x[start:end] @ w[e])
+            start = end
+        return torch.cat(outs)
+    E = offs.numel()
+    if (x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16
+            or offs.dtype != torch.int32 or x.dim() != 2 or w.dim() != 3
+            or offs.dim() != 1 or w.shape[0] != E or w.shape[1] != x.shape[1]
+            or x.shape[1] % 32 or w.shape[2] % 32 or not x.shape[1]
+            or not w.shape[2]):
+        raise ValueError(
+            "moe_grouped_mm(impl='hip'): bf16 x [rows, K] and w [E, K, N] "
+            "with K % 32 == 0 and N % 32 == 0 and int32 offs [E] on the GPU, "
+            f"got {x.dtype} {tuple(x.shape)}, {w.dtype} {tuple(w.shape)}, "
+            f"{offs.dtype} {tuple(offs.shape)}")
+    rows = x.shape[0] * k
+    if not 2 <= E <= MOE_MAX_EXPERTS or rows >= 2 ** 31 or not (
+            1 <= k <= MOE_MAX_TOPK):
+        raise ValueError(
+            f"moe_grouped_mm(impl='hip'): 2 <= E <= {MOE_MAX_EXPERTS}, "
+            f"1 <= k <= {MOE_MAX_TOPK} and rows < 2^31, got E = {E}, "
+            f"k = {k}, rows = {rows}")
+    if gather is not None:
+        if (slot_of_row.dtype != torch.int32 or slot_of_row.numel() != rows
+                or row_of_slot.dtype != torch.int32
+                or row_of_slot.numel() != rows):
+            raise ValueError(
+                "moe_grouped_mm(impl='hip'): gather must be moe_sort's int32 "
+                f"(slot_of_row, row_of_slot) of T * k = {rows} slots and k")
+        slot_of_row = slot_of_row.contiguous()
+        row_of_slot = row_of_slot.contiguous()
+    return _MoEGroupedMM.apply(x, w, offs.contiguous(), slot_of_row,
+                               row_of_slot, int(k))
+
+
 def moe_grouped_mm(
-    x: torch.Tensor, w: torch.Tensor, offs: torch.Tensor
+    x: torch.Tensor, w: torch.Tensor, offs: torch.Tensor,
+    impl: str = "library",
+    gather: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
 ) -> torch.Tensor:
     """Expert GEMMs: rows [offs[e-1], offs[e]) of x [R, K] times w[e] of
-    w [E, K, N] -> [R, N]. This is the library's
-    ``torch.nn.functional.grouped_mm``; where the build rejects it for a
-    device and dtype, a loop over ``offs.tolist()`` (one host sync) takes its
-    place and ``moe_grouped_mm_fallbacks`` counts each such call."""
+    w [E, K, N] -> [R, N].
+
+    ``impl="library"`` is ``torch.nn.functional.grouped_mm``; where the build
+    rejects it for a device and dtype, a loop over ``offs.tolist()`` (one
+    host sync) takes its place and ``moe_grouped_mm_fallbacks`` counts each
+    such call.
+
+    ``impl="hip"`` runs the project's grouped GEMMs (ops/csrc/moe_gemm.hip)
+    forward and backward: no host sync, no atomics, the same bits every call.
+    ``gather=(slot_of_row, row_of_slot, k)``, the pair ``moe_sort`` returned,
+    fuses ``moe_dispatch`` in: x is then the token tensor [T, K], row r reads
+    x[slot_of_row[r] // k] and the result has T*k rows. GPU: bf16 x and w,
+    int32 offs, K % 32 == 0, N % 32 == 0, 2 <= E <= 256, rows < 2^31, else
+    ValueError. On the CPU it is a plain loop over the experts."""
     global moe_grouped_mm_fallbacks
+    if impl == "hip":
+        return _moe_grouped_mm_hip(x, w, offs, gather)
+    if impl != "library":
+        raise ValueError(
+            f"moe_grouped_mm: impl must be 'library' or 'hip', got {impl!r}")
+    if gather is not None:
+        raise ValueError("moe_grouped_mm: gather needs impl='hip'")
     key = (x.device.type, x.dtype)
     grouped_mm = getattr(torch.nn.functional, "grouped_mm", None)
     if grouped_mm is not None and key not in _GROUPED_MM_REJECTED:

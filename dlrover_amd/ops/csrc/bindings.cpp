@@ -11,6 +11,7 @@
 
 #include "attention_launch.h"
 #include "fp8_cast_launch.h"
+#include "moe_gemm_launch.h"
 #include "moe_launch.h"
 
 extern "C" {
@@ -1493,6 +1494,99 @@ std::tuple<at::Tensor, at::Tensor> moe_combine_bwd(
   return {dyp, dw};
 }
 
+// ---- grouped GEMMs of the experts (moe_gemm.hip) ---------------------------
+// bf16 [rows, C] with C % 32 == 0 and 16-byte aligned rows
+void check_moe_gemm_rows(const at::Tensor& t, const char* name) {
+  check_moe_tensor(t, at::kBFloat16, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(1) > 0 && t.size(1) % 32 == 0 &&
+                  t.size(1) < (1LL << 23) && t.size(0) < (1LL << 31) &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              "moe_gemm: ", name,
+              " must be 16-byte aligned [rows < 2^31, C < 2^23], C % 32 == 0");
+}
+
+// offs [E] with 2 <= E <= 256; returns E
+int check_moe_gemm_offs(const at::Tensor& offs) {
+  check_moe_tensor(offs, at::kInt, "offs");
+  TORCH_CHECK(offs.dim() == 1 && offs.numel() >= 2 &&
+                  offs.numel() <= MOE_GEMM_MAX_EXPERTS,
+              "moe_gemm: offs must be [E], 2 <= E <= ", MOE_GEMM_MAX_EXPERTS);
+  return (int)offs.numel();
+}
+
+// w [E, K, N] against the [rows, K] and [rows, N] operands
+void check_moe_gemm_w(const at::Tensor& w, int E, int64_t K, int64_t N) {
+  check_moe_tensor(w, at::kBFloat16, "w");
+  TORCH_CHECK(w.dim() == 3 && w.size(0) == E && w.size(1) == K &&
+                  w.size(2) == N &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "moe_gemm: w must be 16-byte aligned [E, K, N] = [", E, ", ", K,
+              ", ", N, "]");
+}
+
+// The gather of the fused dispatch: slot_of_row [R] over a [T, K], R = T * k.
+// Returns R; without a gather R is a's row count.
+int64_t check_moe_gemm_gather(const at::Tensor& a,
+                              const c10::optional<at::Tensor>& slot_of_row,
+                              int64_t k) {
+  if (!slot_of_row.has_value()) return a.size(0);
+  check_moe_slots(*slot_of_row, a.size(0), k, "slot_of_row");
+  return slot_of_row->numel();
+}
+
+at::Tensor moe_gemm_fwd(const at::Tensor& a, const at::Tensor& w,
+                        const at::Tensor& offs,
+                        c10::optional<at::Tensor> slot_of_row, int64_t k) {
+  check_moe_gemm_rows(a, "a");
+  const int E = check_moe_gemm_offs(offs);
+  TORCH_CHECK(w.dim() == 3, "moe_gemm: w must be [E, K, N]");
+  const int64_t K = a.size(1), N = w.size(2);
+  check_moe_gemm_w(w, E, K, N);
+  TORCH_CHECK(N % 32 == 0 && N < (1LL << 23), "moe_gemm: N % 32 == 0");
+  const int64_t R = check_moe_gemm_gather(a, slot_of_row, k);
+  auto y = at::empty({R, N}, a.options());
+  if (R > 0)
+    moe_gemm_fwd_launch(
+        a.data_ptr(), w.data_ptr(), (const int*)offs.data_ptr(),
+        slot_of_row.has_value() ? (const int*)slot_of_row->data_ptr() : nullptr,
+        y.data_ptr(), R, a.size(0), (int)k, E, (int)K, (int)N, attn_stream());
+  return y;
+}
+
+at::Tensor moe_gemm_dgrad(const at::Tensor& dy, const at::Tensor& w,
+                          const at::Tensor& offs) {
+  check_moe_gemm_rows(dy, "dy");
+  const int E = check_moe_gemm_offs(offs);
+  TORCH_CHECK(w.dim() == 3, "moe_gemm: w must be [E, K, N]");
+  const int64_t K = w.size(1), N = dy.size(1), R = dy.size(0);
+  check_moe_gemm_w(w, E, K, N);
+  TORCH_CHECK(K % 32 == 0 && K < (1LL << 23), "moe_gemm: K % 32 == 0");
+  auto da = at::empty({R, K}, dy.options());
+  if (R > 0)
+    moe_gemm_dgrad_launch(dy.data_ptr(), w.data_ptr(),
+                          (const int*)offs.data_ptr(), da.data_ptr(), R, E,
+                          (int)K, (int)N, attn_stream());
+  return da;
+}
+
+at::Tensor moe_gemm_wgrad(const at::Tensor& a, const at::Tensor& dy,
+                          const at::Tensor& offs,
+                          c10::optional<at::Tensor> slot_of_row, int64_t k) {
+  check_moe_gemm_rows(a, "a");
+  check_moe_gemm_rows(dy, "dy");
+  const int E = check_moe_gemm_offs(offs);
+  const int64_t K = a.size(1), N = dy.size(1);
+  const int64_t R = check_moe_gemm_gather(a, slot_of_row, k);
+  TORCH_CHECK(dy.size(0) == R, "moe_gemm: dy must have ", R, " rows");
+  if (R == 0) return at::zeros({E, K, N}, a.options());
+  auto dw = at::empty({E, K, N}, a.options());
+  moe_gemm_wgrad_launch(
+      a.data_ptr(), dy.data_ptr(), (const int*)offs.data_ptr(),
+      slot_of_row.has_value() ? (const int*)slot_of_row->data_ptr() : nullptr,
+      dw.data_ptr(), R, a.size(0), (int)k, E, (int)K, (int)N, attn_stream());
+  return dw;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1532,6 +1626,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MoE combine backward -> (dyp bf16 [T*k, H], d_topk_w fp32 [T, k])",
         py::arg("dy"), py::arg("yp"), py::arg("topk_w"),
         py::arg("row_of_slot"));
+  m.def("moe_gemm_fwd", &moe_gemm_fwd,
+        "grouped GEMM y[r] = a(r) @ w[e(r)] (bf16, MFMA); a(r) = a[r], or "
+        "a[slot_of_row[r] / k] with the dispatch fused in",
+        py::arg("a"), py::arg("w"), py::arg("offs"), py::arg("slot_of_row"),
+        py::arg("k"));
+  m.def("moe_gemm_dgrad", &moe_gemm_dgrad,
+        "grouped GEMM da[r] = dy[r] @ w[e(r)]^T from the same w", py::arg("dy"),
+        py::arg("w"), py::arg("offs"));
+  m.def("moe_gemm_wgrad", &moe_gemm_wgrad,
+        "grouped GEMM dw[e] = sum over e's rows of a(r)^T dy[r] -> [E, K, N] "
+        "bf16, zeros for an empty expert",
+        py::arg("a"), py::arg("dy"), py::arg("offs"), py::arg("slot_of_row"),
+        py::arg("k"));
   m.def("swiglu_fwd", &swiglu_fwd, "fused SwiGLU forward (bf16)");
   m.def("swiglu_bwd", &swiglu_bwd, "fused SwiGLU backward (bf16)");
   m.def("adamw_step", &adamw_step, "fused AdamW with fp32 master weights");

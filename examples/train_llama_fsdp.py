@@ -35,6 +35,10 @@ def main():
                    help="experts each token is routed to (1..8)")
     p.add_argument("--moe-aux-coef", type=float, default=0.01,
                    help="weight of the load-balancing loss of an MoE model")
+    p.add_argument("--moe-expert-gemm", choices=("library", "hip"),
+                   default="library",
+                   help="hip: the expert GEMMs run on the project's bf16 MFMA "
+                        "grouped GEMM with the token dispatch fused in")
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--batch", type=int, default=1)
     p.add_argument("--seq", type=int, default=4096)
@@ -101,7 +105,8 @@ def main():
         args.seq = min(args.seq, cfg.max_seq_len)
     cfg = dataclasses.replace(cfg, activation_checkpointing=args.act_ckpt,
                               linear_precision=args.linear)
-    moe_kw = {"moe_aux_coef": args.moe_aux_coef}
+    moe_kw = {"moe_aux_coef": args.moe_aux_coef,
+              "moe_expert_gemm": args.moe_expert_gemm}
     if args.experts is not None:
         moe_kw["n_experts"] = args.experts
     if args.experts_per_tok is not None:

@@ -24,6 +24,7 @@ sources = [
     os.path.join(CSRC, "qk_norm_rope.hip"),
     os.path.join(CSRC, "swiglu.hip"),
     os.path.join(CSRC, "moe.hip"),
+    os.path.join(CSRC, "moe_gemm.hip"),
     os.path.join(CSRC, "adamw.hip"),
     os.path.join(CSRC, "multi_tensor.hip"),
     os.path.join(CSRC, "adamw_fp8.hip"),
